@@ -7,6 +7,16 @@ rank per GPU over RCCL.  W untimed warmup steps, then EXACTLY K timed steps
 bracketed by barrier + torch.cuda.synchronize on both sides; elapsed is the
 MAX over ranks; rank 0 prints ONE JSON line.
 
+A plain run does only what the headline figure needs: set up, warm up, time
+the K steps, print the line.  `--full` adds the secondary measurements (the
+separately sampled, per-step-synced p50/p95/p99 latency distribution).
+`--dump-outputs DIR` writes what the last timed step returned (loss,
+accuracy) and the parameters it left behind as DIR/<name>.npy.  Inputs and
+initial weights are seeded, and with this option the last timed step starts
+from the initial weights again, so the dump is one fwd+bwd+update of fixed
+inputs: equal from run to run up to reduction-order rounding, and two builds
+can be compared output for output.
+
 Metric (BASELINE.json): images/sec whole node + p50 step time, MNIST CNN
 sync-SGD, synthetic MNIST-shaped data, random-init weights, bf16 compute on
 GPU.  Weak scaling: per-GPU batch fixed (default 1024 -> global 8192 at
@@ -21,6 +31,27 @@ import time
 import numpy as np
 import torch
 import torch.distributed as dist
+
+
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(out_dir, tensors):
+    """Write each tensor as out_dir/<name>.npy (float32; float64 stays
+    float64).  The whole dump stays under DUMP_BUDGET_BYTES: an array over
+    its share is reduced to a fixed, seeded sample of its elements."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(tensors))
+    for name, t in tensors.items():
+        t = t.detach()
+        t = t.to("cpu", torch.float64 if t.dtype == torch.float64
+                 else torch.float32)
+        a = np.ascontiguousarray(t.numpy())
+        if a.nbytes > share:
+            idx = np.random.default_rng(0).choice(
+                a.size, size=share // a.itemsize, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def main():
@@ -49,6 +80,14 @@ def main():
                     help=">0: drop a rank's gradient past this deadline")
     ap.add_argument("--grad_dtype", default="fp32", choices=["fp32", "bf16"],
                     help="all-reduce wire dtype (fp32 master kept either way)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (per-step "
+                         "synced p50/p95/p99 latency sampling); off by "
+                         "default so a plain run times only the headline")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None,
+                    metavar="DIR",
+                    help="write the last timed step's outputs (loss, "
+                         "accuracy, updated parameters) as DIR/<name>.npy")
     args = ap.parse_args()
     on_gpu_probe = torch.cuda.is_available()
     if args.steps is None:
@@ -109,7 +148,21 @@ def main():
 
     def one_step():
         x, y = ds.next_batch(args.batch_size)
-        trainer.graph_or_eager_step(x, y)
+        return trainer.graph_or_eager_step(x, y)
+
+    # --dump-outputs: the kernels reduce with fp32 atomics, so each step
+    # differs from run to run in the last bits, and hundreds of SGD steps on
+    # random labels amplify that far beyond rounding.  To make the dump
+    # comparable run to run (and build to build), the LAST timed step starts
+    # from the seeded initial parameters again: its batch, step counter and
+    # dropout stream are functions of the arguments alone, so what it
+    # returns is one full fwd+bwd+update of fixed inputs.
+    init_state = None
+    if args.dump_outputs:
+        init_state = (trainer.fp.flat_master.clone(),
+                      None if trainer.flat_momentum is None
+                      else trainer.flat_momentum.clone())
+    dump_at = args.steps - 1 if init_state is not None else -1
 
     for _ in range(args.warmup):
         one_step()
@@ -119,24 +172,44 @@ def main():
     if on_gpu:
         torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last = None
     for i in range(args.steps):
-        one_step()
+        if i == dump_at:
+            # the checkpoint-restore path: master, bf16 shadows, transposes
+            trainer.fp.load_flat(init_state[0])
+            if init_state[1] is not None:
+                trainer.flat_momentum.copy_(init_state[1])
+        last = one_step()
     if on_gpu:
         torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+
+    if args.dump_outputs and rank == 0 and last is not None:
+        # snapshot now: loss/acc are static graph buffers and the parameters
+        # keep training if --full samples more steps below
+        _applied, loss_t, acc_t, _ct = last
+        dump_outputs(args.dump_outputs, {
+            "loss": loss_t, "accuracy": acc_t,
+            "params": trainer.fp.flat_master})
 
     # per-step latency distribution, sampled SEPARATELY with a device sync
     # per step (graph replays enqueue asynchronously, so un-synced per-step
     # wall times are enqueue latencies, not step latencies); the headline
     # elapsed/steps above stays free of per-step sync overhead
-    n_sample = min(args.steps, 30)
-    step_t = np.zeros(n_sample)
-    for i in range(n_sample):
-        ts = time.perf_counter()
-        one_step()
-        if on_gpu:
-            torch.cuda.synchronize()
-        step_t[i] = time.perf_counter() - ts
+    # (--full only: it is 30 more steps a plain run does not need)
+    latency = {}
+    if args.full:
+        n_sample = min(args.steps, 30)
+        step_t = np.zeros(n_sample)
+        for i in range(n_sample):
+            ts = time.perf_counter()
+            one_step()
+            if on_gpu:
+                torch.cuda.synchronize()
+            step_t[i] = time.perf_counter() - ts
+        latency = {
+            f"p{p}_ms_per_step": round(float(np.percentile(step_t, p)) * 1000, 4)
+            for p in (50, 95, 99)}
     if trainer.mode == "interval":
         # drain outstanding interval aggregations so every rank leaves the
         # communicator with a matched collective count
@@ -171,9 +244,7 @@ def main():
                 "global_batch": args.batch_size * n_gpus,
                 "seq_len": None,
                 "parallelism": f"dp{n_gpus}",
-                "p50_ms_per_step": round(float(np.percentile(step_t, 50)) * 1000, 4),
-                "p95_ms_per_step": round(float(np.percentile(step_t, 95)) * 1000, 4),
-                "p99_ms_per_step": round(float(np.percentile(step_t, 99)) * 1000, 4),
+                **latency,
                 # the engine mode that actually ran (k_of_n degenerates to
                 # full_sync at world=1 — reported honestly, never relabeled)
                 "mode": trainer.mode,

@@ -40,7 +40,7 @@ def test_bench_json_schema_complete():
     round's BENCH record)."""
     out = subprocess.run(
         [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3",
-         "--warmup", "1", "--batch_size", "32"],
+         "--warmup", "1", "--batch_size", "32", "--full"],
         capture_output=True, text=True, timeout=240, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     j = _last_json_line(out.stdout)
@@ -64,6 +64,32 @@ def test_bench_json_schema_complete():
     # whole-job aggregate identity: value = global_batch * steps / elapsed
     approx = cfg["global_batch"] / (j["ms_per_step"] / 1000.0)
     assert abs(j["value"] - approx) < 0.01 * approx
+
+
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """A plain run (no --full) skips the per-step-synced latency sampling,
+    and --dump-outputs writes the last timed step's loss/accuracy and the
+    parameters it left behind as float32 .npy files."""
+    import numpy as np
+    d = tmp_path / "dump"
+    out = subprocess.run(
+        [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1",
+         "--steps", "3", "--warmup", "1", "--batch_size", "32",
+         "--dump-outputs", str(d)],
+        capture_output=True, text=True, timeout=240, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    j = _last_json_line(out.stdout)
+    assert j["steps"] == 3 and j["ms_per_step"] > 0
+    assert not [k for k in j["config"] if k.endswith("_ms_per_step")]
+    assert sorted(p.name for p in d.iterdir()) == [
+        "accuracy.npy", "loss.npy", "params.npy"]
+    arrs = {p.stem: np.load(p) for p in d.iterdir()}
+    assert all(a.dtype == np.float32 for a in arrs.values())
+    assert arrs["loss"].size == 1 and np.isfinite(arrs["loss"]).all()
+    assert arrs["accuracy"].size == 1
+    assert 0.0 <= float(arrs["accuracy"].reshape(-1)[0]) <= 1.0
+    assert arrs["params"].size > 1000 and np.isfinite(arrs["params"]).all()
+    assert sum(a.nbytes for a in arrs.values()) <= 64 * 1000 * 1000
 
 
 @pytest.mark.timeout(300)
@@ -107,6 +133,17 @@ def test_bench_mode_k_of_n_honest_at_world1():
     assert j["config"]["mode"] == "full_sync"
 
 
+def _two_rank_env():
+    """Env for a 2-rank launch: on a box with ONE visible GPU both ranks map
+    onto it (bench.py's modulo map) and RCCL refuses duplicate devices, so
+    the ranks talk over gloo there, as bench.py documents."""
+    import torch
+    env = dict(os.environ)
+    if torch.cuda.device_count() == 1:
+        env["DMNIST_BACKEND"] = "gloo"
+    return env
+
+
 @pytest.mark.timeout(600)
 def test_bench_torchrun_2proc_k_of_n():
     """2-rank k_of_n bench: the mode engages for real (K=1 of 2)."""
@@ -117,7 +154,8 @@ def test_bench_torchrun_2proc_k_of_n():
          os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3",
          "--warmup", "1", "--batch_size", "32", "--mode", "k_of_n",
          "--replicas_to_aggregate", "1"],
-        capture_output=True, text=True, timeout=540, cwd=ROOT)
+        capture_output=True, text=True, timeout=540, cwd=ROOT,
+        env=_two_rank_env())
     assert out.returncode == 0, out.stderr[-3000:]
     j = _last_json_line(out.stdout)
     assert j["config"]["mode"] == "k_of_n"
@@ -125,7 +163,7 @@ def test_bench_torchrun_2proc_k_of_n():
 
 @pytest.mark.timeout(600)
 def test_bench_torchrun_2proc():
-    env = dict(os.environ)
+    env = _two_rank_env()
     out = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
          "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
@@ -138,6 +176,42 @@ def test_bench_torchrun_2proc():
     assert j["n_gpus"] == 2
     assert j["config"]["global_batch"] == 64
     assert j["config"]["parallelism"] == "dp2"
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_repeatable_on_gpu(tmp_path):
+    """Two runs with the same arguments must dump the same arrays up to
+    rounding.  The dumped step is one fwd+bwd+update from the seeded initial
+    parameters, so the only run-to-run freedom is the order of the fp32
+    atomic reductions.  Bounds (lr = 0.01, batch 1024):
+      loss      mean of 1024 fp32 terms, reorder error <~ sqrt(1024) * 2^-24
+                relative; 1e-4 leaves room for one bf16 logit flipping an ulp
+      accuracy  a count / 1024: at most one argmax tie may flip
+      params    delta = lr * delta_grad; a reordered sum of K <= 1024*784
+                terms moves by <~ sqrt(K) * 2^-24 ~ 5e-5 of a gradient of
+                scale <~ 10, so lr * 10 * 1e-4 = 1e-5 absolute
+    """
+    import numpy as np
+
+    def run(tag):
+        d = tmp_path / tag
+        out = subprocess.run(
+            [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1",
+             "--steps", "50", "--warmup", "10", "--dump-outputs", str(d)],
+            capture_output=True, text=True, timeout=240, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        return {n: np.load(d / f"{n}.npy").astype(np.float64)
+                for n in ("loss", "accuracy", "params")}
+
+    a, b = run("a"), run("b")
+    d_loss = float(np.abs(a["loss"] - b["loss"]).max())
+    d_acc = float(np.abs(a["accuracy"] - b["accuracy"]).max())
+    d_par = float(np.abs(a["params"] - b["params"]).max())
+    print(f"dump repeatability: dloss={d_loss:.3e} dacc={d_acc:.3e} "
+          f"dparams={d_par:.3e}")
+    assert d_loss <= 1e-4 * float(np.abs(a["loss"]).max())
+    assert d_acc <= 1.0 / 1024 + 1e-9
+    assert d_par <= 1e-5
 
 
 @pytest.mark.gpu

@@ -36,12 +36,12 @@ CASES = [
 ]
 
 
-def _run(rank, world, port, extra, q):
+def _run(rank, world, port, extra, train_dir, q):
     init_pg(rank, world, port)
     from distributedmnist_amd.engine.train import Trainer, make_dataset
     from distributedmnist_amd.utils.flags import build_train_parser
     flags = build_train_parser().parse_args(
-        ["--synthetic_data", "--train_dir", f"/tmp/dmnist_matrix_{port}",
+        ["--synthetic_data", "--train_dir", train_dir,
          "--batch_size", "16", "--max_steps", "6", "--model", "mlp",
          "--device", "cpu", "--save_interval_secs", "100000"] + extra)
     t = Trainer(flags, rank=rank, world=world, local_rank=rank)
@@ -56,19 +56,19 @@ def _run(rank, world, port, extra, q):
 @pytest.mark.parametrize("extra,must_match",
                          CASES, ids=[" ".join(c[0]) or "default"
                                      for c in CASES])
-def test_flag_matrix_world2(extra, must_match):
-    res = spawn_collect(_run, 2, args=(extra,))
+def test_flag_matrix_world2(extra, must_match, tmp_path):
+    res = spawn_collect(_run, 2, args=(extra, str(tmp_path / "td")))
     res = {r: (v[0], tuple(v[1])) for r, v in res.items()}
     if must_match:
         assert res[0] == res[1], (extra, res)
 
 
-def _run_wire_traj(rank, world, port, grad_dtype, q):
+def _run_wire_traj(rank, world, port, grad_dtype, train_dir, q):
     init_pg(rank, world, port)
     from distributedmnist_amd.engine.train import Trainer, make_dataset
     from distributedmnist_amd.utils.flags import build_train_parser
     flags = build_train_parser().parse_args(
-        ["--synthetic_data", "--train_dir", f"/tmp/dmnist_wt_{port}",
+        ["--synthetic_data", "--train_dir", train_dir,
          "--batch_size", "16", "--max_steps", "20", "--model", "mlp",
          "--device", "cpu", "--save_interval_secs", "100000",
          "--grad_dtype", grad_dtype])
@@ -80,14 +80,15 @@ def _run_wire_traj(rank, world, port, grad_dtype, q):
 
 
 @pytest.mark.timeout(240)
-def test_bf16_wire_trajectory_tracks_fp32():
+def test_bf16_wire_trajectory_tracks_fp32(tmp_path):
     """20-step 2-rank trajectories with fp32 vs bf16 gradient wire must
     stay close (bf16 rounds each reduce; fp32 master updates otherwise
     identical) — the numerics guard for --grad_dtype bf16."""
     import torch as _torch
 
     def run(dtype):
-        res = spawn_collect(_run_wire_traj, 2, args=(dtype,))
+        res = spawn_collect(_run_wire_traj, 2,
+                            args=(dtype, str(tmp_path / dtype)))
         assert _torch.equal(res[0][0], res[1][0])
         return res[0][0]
 

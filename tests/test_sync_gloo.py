@@ -66,8 +66,8 @@ def _run_timeout(rank, world, port, q):
     dist.destroy_process_group()
 
 
-def _spawn(fn, world=2):
-    return spawn_collect(fn, world)
+def _spawn(fn, world=2, args=()):
+    return spawn_collect(fn, world, args=args)
 
 
 @pytest.mark.timeout(120)
@@ -177,12 +177,12 @@ def test_interval_3rank_jittered_agreement():
     assert len(finals) == 1, finals  # same aggregated grad everywhere
 
 
-def _run_trainer_interval_e2e(rank, world, port, q):
+def _run_trainer_interval_e2e(rank, world, port, train_dir, q):
     _init(rank, world, port)
     from distributedmnist_amd.engine.train import Trainer, make_dataset
     from distributedmnist_amd.utils.flags import build_train_parser
     flags = build_train_parser().parse_args(
-        ["--synthetic_data", "--train_dir", f"/tmp/dmnist_iv_test_{port}",
+        ["--synthetic_data", "--train_dir", train_dir,
          "--batch_size", "16", "--max_steps", "25", "--model", "mlp",
          "--device", "cpu", "--interval_method", "--interval_ms", "40",
          "--inject_slow_rank", "1", "--inject_slow_ms", "25"])
@@ -195,8 +195,8 @@ def _run_trainer_interval_e2e(rank, world, port, q):
 
 
 @pytest.mark.timeout(180)
-def test_trainer_interval_e2e_params_identical_after_drain():
-    res = _spawn(_run_trainer_interval_e2e)
+def test_trainer_interval_e2e_params_identical_after_drain(tmp_path):
+    res = _spawn(_run_trainer_interval_e2e, args=(str(tmp_path / "td"),))
     assert res[0] == res[1], "ranks diverged in interval mode"
     assert res[0][0] > 0, "no interval aggregation ever fired"
 
@@ -261,12 +261,12 @@ def test_drop_connect_pre_aggregation_masks_are_rank_distinct():
         assert abs(p0 + p1 + p2 - 1.0) < 1e-6
 
 
-def _run_trainer_e2e(rank, world, port, q):
+def _run_trainer_e2e(rank, world, port, train_dir, q):
     _init(rank, world, port)
     from distributedmnist_amd.engine.train import Trainer, make_dataset
     from distributedmnist_amd.utils.flags import build_train_parser
     flags = build_train_parser().parse_args(
-        ["--synthetic_data", "--train_dir", f"/tmp/dmnist_e2e_test_{port}",
+        ["--synthetic_data", "--train_dir", train_dir,
          "--batch_size", "16", "--max_steps", "5", "--model", "mlp",
          "--device", "cpu"])
     t = Trainer(flags, rank=rank, world=world, local_rank=rank)
@@ -278,8 +278,8 @@ def _run_trainer_e2e(rank, world, port, q):
 
 
 @pytest.mark.timeout(180)
-def test_trainer_e2e_params_identical_across_ranks():
-    res = _spawn(_run_trainer_e2e)
+def test_trainer_e2e_params_identical_across_ranks(tmp_path):
+    res = _spawn(_run_trainer_e2e, args=(str(tmp_path / "td"),))
     assert res[0] == res[1], "ranks diverged after 5 sync steps"
 
 
