@@ -724,6 +724,45 @@ void grad_mask(torch::Tensor g, double keep, int64_t seed, int64_t step,
                    cur_stream());
 }
 
+void batch_gather(torch::Tensor img_u8, torch::Tensor lab_u8,
+                  torch::Tensor lut, torch::Tensor x, torch::Tensor y,
+                  int64_t seed, int64_t step,
+                  c10::optional<torch::Tensor> step_dev) {
+  CHECK_CUDA(img_u8); CHECK_CONTIG(img_u8);
+  CHECK_CUDA(lab_u8); CHECK_CONTIG(lab_u8);
+  CHECK_CUDA(lut); CHECK_BF16(lut); CHECK_CONTIG(lut);
+  CHECK_CUDA(x); CHECK_BF16(x); CHECK_CONTIG(x);
+  CHECK_CUDA(y); CHECK_CONTIG(y);
+  TORCH_CHECK(img_u8.scalar_type() == at::kByte &&
+              lab_u8.scalar_type() == at::kByte,
+              "batch_gather: images/labels must be uint8");
+  TORCH_CHECK(y.scalar_type() == at::kLong, "batch_gather: y must be int64");
+  const int64_t N = lab_u8.numel(), B = y.numel();
+  TORCH_CHECK(N >= 1 && N < (int64_t(1) << 31),
+              "batch_gather: N out of range");
+  TORCH_CHECK(B >= 1 && B <= N, "batch_gather: batch size ", B,
+              " must be in [1, N=", N, "]");
+  TORCH_CHECK(img_u8.numel() == N * 784, "batch_gather: images must be [N,784]");
+  TORCH_CHECK(x.numel() == B * 784, "batch_gather: x must hold B*784 values");
+  TORCH_CHECK(lut.numel() == 256, "batch_gather: lut must have 256 entries");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(img_u8.data_ptr()) % 8 == 0 &&
+              reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "batch_gather: images must be 8B- and x 16B-aligned");
+  const long* sd = nullptr;
+  if (step_dev.has_value() && step_dev->defined()) {
+    TORCH_CHECK(step_dev->is_cuda() && step_dev->scalar_type() == at::kLong &&
+                step_dev->numel() >= 1, "batch_gather: step_dev must be a "
+                "device int64 tensor");
+    sd = step_dev->data_ptr<long>();
+  } else {
+    TORCH_CHECK(step >= 0, "batch_gather: step must be >= 0");
+  }
+  launch_batch_gather(img_u8.data_ptr<uint8_t>(), lab_u8.data_ptr<uint8_t>(),
+                      bf16_ptr(lut), bf16_mut(x), y.data_ptr<long>(),
+                      (uint32_t)N, (uint32_t)B, (uint64_t)seed,
+                      (uint64_t)step, sd, cur_stream());
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -785,6 +824,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "reference distributed_train.py:194-203)",
         py::arg("g"), py::arg("keep"), py::arg("seed"), py::arg("step"),
         py::arg("rank"), py::arg("base") = 0,
+        py::arg("step_dev") = c10::nullopt);
+  m.def("batch_gather", &batch_gather,
+        "gather one training batch from the device-resident uint8 set "
+        "(Feistel epoch permutation keyed on seed + step; LUT-normalised "
+        "to bf16) into x [B,28,28,1] bf16 / y [B] int64",
+        py::arg("img_u8"), py::arg("lab_u8"), py::arg("lut"), py::arg("x"),
+        py::arg("y"), py::arg("seed"), py::arg("step"),
         py::arg("step_dev") = c10::nullopt);
   m.def("linear_act_fwd_dev", &linear_act_fwd_dev,
         "linear fwd with device-side dropout offset",

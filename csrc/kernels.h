@@ -76,6 +76,12 @@ void launch_grad_mask(float* g, long n, long base, float keep, uint64_t seed,
 void launch_step_advance(long* step_dev, float* lr_scale_dev, float lr0,
                          float decay, int decay_steps, float inv_contrib,
                          hipStream_t);
+// data_gather.hip — batch gather from the device-resident uint8 training set
+// (stateless Feistel epoch permutation keyed on seed + step / step_dev)
+void launch_batch_gather(const uint8_t* img, const uint8_t* lab,
+                         const unsigned short* lut, unsigned short* x,
+                         long* y, uint32_t N, uint32_t B, uint64_t seed,
+                         uint64_t step, const long* step_dev, hipStream_t);
 void launch_transpose_bf16(const unsigned short* src, unsigned short* dst,
                            int R, int C, hipStream_t);
 struct TransposeDesc {

@@ -1,0 +1,136 @@
+"""Device-resident MNIST training set with a stateless batch sequence.
+
+The whole training set stays on the device as uint8 (47 MB for 60000
+images); a batch is built by ONE gather (ops/functional.py::batch_gather —
+the HIP batch_gather_kernel for bf16 on a GPU, the torch reference
+elsewhere) that permutes, normalises through a 256-entry LUT and writes
+straight into the caller's buffers.  No host array is touched per step.
+
+The sample order is a pure function of (seed, step): epoch = step // spe
+with spe = N // B batches per epoch (the N % B tail is dropped, as
+DataSet.next_batch drops it), epoch 0 unshuffled (as DataSet), later epochs
+ordered by a cycle-walking Feistel permutation keyed on (seed, epoch) —
+ops/cpu_ref.py::feistel_perm.  A resumed run that seeks to its restored step
+therefore sees exactly the batches an uninterrupted run would have seen.
+"""
+
+from __future__ import annotations
+
+import os
+
+import numpy as np
+import torch
+
+from ..ops import functional as Fx
+from .mnist_data import (IMAGE_SIZE, NUM_CHANNELS, PIXEL_DEPTH, TRAIN_IMAGES,
+                         TRAIN_LABELS, extract_images_u8, extract_labels)
+
+
+def normalisation_lut(dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """lut[v] = (v - 127.5) / 255 — extract_images' normalisation, evaluated
+    in fp32 and rounded once to `dtype` (the same rounding the host-fed path
+    applies when it casts its fp32 batch)."""
+    lut = (torch.arange(256).float() - PIXEL_DEPTH / 2.0) / PIXEL_DEPTH
+    return lut.to(dtype)
+
+
+class DeviceDataSet:
+    """Drop-in for DataSet whose data lives on `device` as uint8.
+
+    images_u8: [N, 784] (or [N,28,28[,1]]) uint8; labels: [N] integer < 256.
+    Sharding follows DataSet: rank::world slices unless shard=False.
+    """
+
+    def __init__(self, images_u8, labels_u8, worker_id: int = 0,
+                 n_workers: int = 1, shard: bool = True, seed: int = 0,
+                 device="cpu", dtype: torch.dtype = torch.float32):
+        images_u8 = np.asarray(images_u8)
+        labels_u8 = np.asarray(labels_u8)
+        if images_u8.dtype != np.uint8:
+            raise TypeError("DeviceDataSet wants raw uint8 pixels")
+        assert images_u8.shape[0] == labels_u8.shape[0]
+        images_u8 = images_u8.reshape(images_u8.shape[0], -1)
+        assert images_u8.shape[1] == IMAGE_SIZE * IMAGE_SIZE * NUM_CHANNELS
+        if shard and n_workers > 1:
+            images_u8 = images_u8[worker_id::n_workers]
+            labels_u8 = labels_u8[worker_id::n_workers]
+        self._num_examples = int(images_u8.shape[0])
+        self.device = torch.device(device)
+        self.dtype = dtype
+        self.seed = int(seed)
+        # one private contiguous copy (the loader's arrays are read-only
+        # views of the file buffer, shards are strided views)
+        self._images = torch.from_numpy(np.array(images_u8)).to(self.device)
+        self._labels = torch.from_numpy(
+            np.array(labels_u8, dtype=np.uint8)).to(self.device)
+        self._lut = normalisation_lut(dtype).to(self.device)
+        self._cursor = 0
+
+    @property
+    def images(self):
+        return self._images
+
+    @property
+    def labels(self):
+        return self._labels
+
+    @property
+    def num_examples(self):
+        return self._num_examples
+
+    @property
+    def epochs_completed(self):
+        return None  # depends on the batch size: steps // (N // B)
+
+    # -- stateless access ------------------------------------------------
+    def gather_into(self, x: torch.Tensor, y: torch.Tensor, step=None,
+                    step_dev=None):
+        """Write the batch at `step` (host int) or `*step_dev` (device
+        int64; capturable into a hipGraph) into x [B,28,28,1] / y [B]."""
+        if x.dtype != self.dtype:
+            raise TypeError(f"x is {x.dtype}, data set built for {self.dtype}")
+        return Fx.batch_gather(self._images, self._labels, self._lut, x, y,
+                               self.seed, step=step, step_dev=step_dev)
+
+    def batch_at(self, step: int, batch_size: int):
+        """(x, y) of the batch at `step` — a pure function of its arguments
+        (and the seed)."""
+        if batch_size > self._num_examples:
+            raise ValueError(f"batch size {batch_size} exceeds the "
+                             f"{self._num_examples} examples of this rank")
+        x = torch.empty((batch_size, IMAGE_SIZE, IMAGE_SIZE, NUM_CHANNELS),
+                        dtype=self.dtype, device=self.device)
+        y = torch.empty(batch_size, dtype=torch.int64, device=self.device)
+        return self.gather_into(x, y, step=int(step))
+
+    # -- DataSet-style cursor ---------------------------------------------
+    def seek(self, step: int):
+        self._cursor = int(step)
+
+    def next_batch(self, batch_size: int):
+        out = self.batch_at(self._cursor, batch_size)
+        self._cursor += 1
+        return out
+
+
+def load_device_mnist(data_dir: str, subset: int = 0, worker_id: int = 0,
+                      n_workers: int = 1, shard: bool = True, seed: int = 0,
+                      device="cpu", dtype: torch.dtype = torch.float32):
+    """idx-gz train files -> DeviceDataSet holding exactly the examples the
+    host-fed path (engine/train.py::make_dataset) trains on: the rank::world
+    shard unless shard=False, then `subset` keeps its first N examples."""
+    paths = [os.path.join(data_dir, f) for f in (TRAIN_IMAGES, TRAIN_LABELS)]
+    missing = [p for p in paths if not os.path.exists(p)]
+    if missing:
+        raise FileNotFoundError(
+            f"MNIST files missing under {data_dir}: {missing}. This "
+            "environment has no network; place the idx-gz files there or use "
+            "--subset/fake data / synthetic mode.")
+    images = extract_images_u8(paths[0])
+    labels = extract_labels(paths[1])
+    if shard and n_workers > 1:
+        images, labels = images[worker_id::n_workers], labels[worker_id::n_workers]
+    if subset:
+        images, labels = images[:subset], labels[:subset]
+    return DeviceDataSet(images, labels, shard=False, seed=seed,
+                         device=device, dtype=dtype)

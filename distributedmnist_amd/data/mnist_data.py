@@ -51,6 +51,20 @@ def extract_images(path: str, num_images: int | None = None) -> np.ndarray:
         return data.reshape(n, rows, cols, NUM_CHANNELS)
 
 
+def extract_images_u8(path: str, num_images: int | None = None) -> np.ndarray:
+    """idx3-ubyte.gz -> [N, rows*cols] uint8, the raw pixels (no
+    normalisation): what DeviceDataSet keeps resident on the device."""
+    import struct
+    with gzip.open(path) as f:
+        magic, n, rows, cols = struct.unpack(">IIII", f.read(16))
+        if magic != 2051:
+            raise ValueError(f"{path}: bad idx3 magic {magic}")
+        if num_images is not None:
+            n = min(n, num_images)
+        buf = f.read(rows * cols * n * NUM_CHANNELS)
+        return np.frombuffer(buf, dtype=np.uint8).reshape(n, rows * cols)
+
+
 def extract_labels(path: str, num_images: int | None = None) -> np.ndarray:
     import struct
     with gzip.open(path) as f:
@@ -61,6 +75,30 @@ def extract_labels(path: str, num_images: int | None = None) -> np.ndarray:
             n = min(n, num_images)
         buf = f.read(n)
         return np.frombuffer(buf, dtype=np.uint8).astype(np.int64)
+
+
+def write_random_idx(data_dir: str, n_train: int, n_test: int,
+                     seed: int = 0) -> None:
+    """Write seeded-random but VALID MNIST idx-gz files (all four) under
+    `data_dir` — stand-ins for the real files in benchmarks and tests of
+    the real-data path (there is no download here)."""
+    import struct
+    rng = np.random.RandomState(seed)
+    os.makedirs(data_dir, exist_ok=True)
+    for img_name, lab_name, n in ((TRAIN_IMAGES, TRAIN_LABELS, n_train),
+                                  (TEST_IMAGES, TEST_LABELS, n_test)):
+        pixels = rng.randint(0, 256, size=n * IMAGE_SIZE * IMAGE_SIZE,
+                             dtype=np.uint8)
+        labels = rng.randint(0, NUM_LABELS, size=n, dtype=np.uint8)
+        # compresslevel 1: random bytes do not compress; keep writing fast
+        with gzip.open(os.path.join(data_dir, img_name), "wb",
+                       compresslevel=1) as f:
+            f.write(struct.pack(">IIII", 2051, n, IMAGE_SIZE, IMAGE_SIZE))
+            f.write(pixels.tobytes())
+        with gzip.open(os.path.join(data_dir, lab_name), "wb",
+                       compresslevel=1) as f:
+            f.write(struct.pack(">II", 2049, n))
+            f.write(labels.tobytes())
 
 
 class DataSet:

@@ -10,6 +10,10 @@ pieces that change per step live in DEVICE memory:
 advanced INSIDE the graph by the step_advance kernel at the END of the body
 (so the values seen by the body equal the eager schedule's).
 
+With a DeviceDataSet attached (--device_data) even the two batch copies go:
+the batch gather, keyed on step_dev, is captured at the head of the body
+and run_resident() is the replay alone.
+
 Only the full_sync mode is graphable (K-of-N / interval / CDF need
 data-dependent host control flow); Trainer falls back to eager elsewhere.
 
@@ -39,9 +43,14 @@ log = logging.getLogger("dmnist.graph")
 
 
 class GraphedStep:
-    def __init__(self, trainer, batch_shape, split: bool = False):
+    def __init__(self, trainer, batch_shape, split: bool = False,
+                 dataset=None):
         t = trainer
         self.split = split
+        # resident input pipeline: when a DeviceDataSet is attached, its
+        # batch gather (keyed on step_dev) is captured at the head of the
+        # body and run_resident() replays with no host-side batch copies
+        self.ds = dataset
         assert t.device.type == "cuda", "GraphedStep requires a GPU"
         assert t.engine.timeout_s is None and (
             t.mode == "full_sync" or (t.mode == "cdf" and t.world == 1)), \
@@ -99,6 +108,7 @@ class GraphedStep:
             self._fused.overlap_allreduce = False
 
         self._prime(t.step)
+        self._next_step = t.step
         torch.cuda.synchronize()
         # Warmup is COLLECTIVE-FREE: it trains 3 throwaway steps on zero
         # images whose state is rolled back below, so skipping the
@@ -139,11 +149,22 @@ class GraphedStep:
         cur_stream = torch.cuda.current_stream()
         self.graph = torch.cuda.CUDAGraph()
         self.graph_b = torch.cuda.CUDAGraph() if self.two_graph else None
+        # An earlier Trainer of this process dies as a reference cycle
+        # (Trainer <-> GraphedStep) that owns hipGraphs and their memory
+        # pool.  If the cyclic collector frees it in the MIDDLE of the
+        # capture below, that teardown aborts the process (torch.cuda.graph
+        # no longer collects on entry).  Collect now and keep the collector
+        # off until the capture has ended.
+        import gc
+        gc.collect()
+        gc_was_enabled = gc.isenabled()
+        gc.disable()
         try:
             if self.two_graph:
                 with torch.cuda.graph(self.graph):
                     # no grad-bucket fill: the previous replay's SGD tail
                     # zeroed it (zero_grad=True), and warmup left it zeroed
+                    self._gather()
                     loss, acc = self._fused.stage_fc(
                         self.static_x, self.static_y, self.step_dev)
                     if self.dc_pre:
@@ -198,6 +219,9 @@ class GraphedStep:
             except Exception:
                 pass
             raise
+        finally:
+            if gc_was_enabled:
+                gc.enable()
 
         # restore pre-warmup state
         t.fp.flat_master.copy_(master0)
@@ -215,6 +239,13 @@ class GraphedStep:
               flags.learning_rate_decay_factor ** (step // self.decay_steps))
         self.lr_scale_dev.fill_(lr * self.inv_contrib)
 
+    def _gather(self):
+        """Resident input: build this step's batch in the static slots from
+        the device step counter (no-op without an attached dataset)."""
+        if self.ds is not None:
+            self.ds.gather_into(self.static_x, self.static_y,
+                                step_dev=self.step_dev)
+
     def _body_grads(self):
         """fwd + bwd: gradients land in the flat bucket; returns True if
         the fused step already issued the bucketed all-reduce."""
@@ -222,6 +253,7 @@ class GraphedStep:
         fp = t.fp
         # grad bucket already zero: the SGD tail clears it after consuming
         fused_reduced = False
+        self._gather()
         if self._fused is not None:
             loss, acc = self._fused(self.static_x, self.static_y,
                                     self.step_dev)
@@ -280,8 +312,29 @@ class GraphedStep:
 
     def run(self, images, labels):
         """Replay one step. Returns (loss, acc) static device tensors."""
+        if self.ds is not None:
+            raise RuntimeError(
+                "this graph gathers its own batch from the attached "
+                "DeviceDataSet (it would overwrite the one passed in): "
+                "use run_resident()")
         self.static_x.copy_(images, non_blocking=True)
         self.static_y.copy_(labels, non_blocking=True)
+        return self._replay()
+
+    def run_resident(self):
+        """Replay one step on the batch the captured gather builds from
+        step_dev: no per-step host work besides the replay itself."""
+        if self.ds is None:
+            raise RuntimeError("run_resident() needs a graph captured with "
+                               "an attached DeviceDataSet")
+        if self._next_step != self.t.step:
+            # the trainer's step moved outside this graph (eager steps in
+            # between): re-key the device counter + LR so the gather, the
+            # dropout stream and the staircase follow the trainer
+            self._prime(self.t.step)
+        return self._replay()
+
+    def _replay(self):
         self.graph.replay()
         if self.two_graph:
             t = self.t
@@ -305,13 +358,14 @@ class GraphedStep:
                 t.engine.wire_allreduce(t.fp.flat_grad)
             self._tail()
         self.t.step += 1
+        self._next_step = self.t.step
         return self.static_loss, self.static_acc
 
 
-def try_graph(trainer, batch_shape, split: bool = False):
+def try_graph(trainer, batch_shape, split: bool = False, dataset=None):
     """Build a GraphedStep, or None if capture is unsupported here."""
     try:
-        return GraphedStep(trainer, batch_shape, split=split)
+        return GraphedStep(trainer, batch_shape, split=split, dataset=dataset)
     except Exception as e:  # noqa: BLE001 — fall back to eager on any failure
         log.warning("hipGraph capture unavailable (%s); running eager", e)
         return None

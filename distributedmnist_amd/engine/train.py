@@ -26,7 +26,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from ..data import SyntheticDataSet
+from ..data import DeviceDataSet, SyntheticDataSet
 from ..models import build_model
 from ..ops import functional as Fx
 from ..parallel import FlatParams, StepTimer, SyncEngine
@@ -123,6 +123,7 @@ class Trainer:
         self._eager_fused = None
         self._eager_fused_tried = False
         self._step_dev = None
+        self._resident_ds = None  # DeviceDataSet (attach_dataset)
         self.flat_momentum = (torch.zeros_like(self.fp.flat_master)
                               if flags.momentum > 0 else None)
         # parameter-init parity across ranks (broadcast once)
@@ -141,9 +142,47 @@ class Trainer:
         labels = labels.to(device=self.device, non_blocking=True)
         return images, labels
 
+    def attach_dataset(self, ds):
+        """Make `ds` (a DeviceDataSet on this trainer's device) the step's
+        input: resident_step() gathers its batches on the device — inside
+        the captured hipGraph when the step is graphable.  Attach before
+        the first step: the capture decides once whether it holds the
+        gather."""
+        if not isinstance(ds, DeviceDataSet):
+            raise TypeError("attach_dataset wants a DeviceDataSet")
+        if (ds.images.device != self.fp.flat_master.device
+                or ds.dtype != self.compute_dtype):
+            raise ValueError(
+                f"dataset lives on {ds.device}/{ds.dtype}, trainer computes "
+                f"on {self.device}/{self.compute_dtype}")
+        if self._graph_tried:
+            raise RuntimeError("attach_dataset must precede the first step")
+        if self.flags.batch_size > ds.num_examples:
+            raise ValueError(f"batch size {self.flags.batch_size} exceeds "
+                             f"the {ds.num_examples} examples of this rank")
+        self._resident_ds = ds
+        self._num_examples = ds.num_examples
+
+    def resident_step(self):
+        """One step on the attached dataset's batch at self.step; same
+        return as graph_or_eager_step.  Graph path: one replay, no host
+        batch work.  Eager path (any sync mode): gather, then train_step."""
+        ds = self._resident_ds
+        if ds is None:
+            raise RuntimeError("resident_step() needs attach_dataset() first")
+        bs = self.flags.batch_size
+        g = self._get_graph((bs, 28, 28, 1))
+        if g is not None:
+            return self._graph_step(g.run_resident)
+        x, y = ds.batch_at(self.step, bs)
+        return self.train_step(x, y)
+
     def get_graph(self, images):
         """hipGraph-captured step when eligible (GPU, full_sync, no
         injection/timing instrumentation); None -> eager path."""
+        return self._get_graph(tuple(images.shape))
+
+    def _get_graph(self, batch_shape):
         if self._graph is not None:
             return self._graph
         if self._graph_tried:
@@ -160,6 +199,10 @@ class Trainer:
                     and self.engine.timeout_s is None
                     and flags.inject_slow_rank < 0
                     and getattr(flags, "hip_graph", "auto") != "off")
+        if self._resident_ds is not None:
+            # only the HIP gather is capturable (the fp32 reference form
+            # reads step_dev on the host)
+            eligible = eligible and self.compute_dtype == torch.bfloat16
         if eligible:
             from .graphstep import try_graph
             # capture scope: world > 1 captures the COMPUTE only (split) so
@@ -172,7 +215,8 @@ class Trainer:
                           or bool(os.environ.get("DMNIST_FORCE_GRAPH")))
             split = (self.world > 1 and dist.is_initialized()
                      and not force_full)
-            self._graph = try_graph(self, tuple(images.shape), split=split)
+            self._graph = try_graph(self, batch_shape, split=split,
+                                    dataset=self._resident_ds)
         if self.world > 1 and dist.is_initialized():
             # ALL ranks must agree on graph-vs-eager: the graphed fused step
             # issues a bucketed 2-collective sequence, eager issues one —
@@ -203,20 +247,25 @@ class Trainer:
         """Preferred step entry: graph replay when available."""
         g = self.get_graph(images)
         if g is not None:
-            if self.mode == "cdf":
-                step = self.step
-                self.engine.step_begin(step)
-                e0, e1 = self._cdf_event_pair()
-                e0.record()
-                loss, acc = g.run(images, labels)
-                e1.record()
-                self._cdf_steps.append(step)
-                if len(self._cdf_steps) >= self.engine.cdf_log_every:
-                    self._flush_cdf()
-                return True, loss, acc, 0.0
-            loss, acc = g.run(images, labels)
-            return True, loss, acc, 0.0
+            return self._graph_step(lambda: g.run(images, labels))
         return self.train_step(images, labels)
+
+    def _graph_step(self, replay):
+        """One graph replay (`replay` -> (loss, acc)), with the batched
+        hipEvent timing around it in cdf mode."""
+        if self.mode == "cdf":
+            step = self.step
+            self.engine.step_begin(step)
+            e0, e1 = self._cdf_event_pair()
+            e0.record()
+            loss, acc = replay()
+            e1.record()
+            self._cdf_steps.append(step)
+            if len(self._cdf_steps) >= self.engine.cdf_log_every:
+                self._flush_cdf()
+            return True, loss, acc, 0.0
+        loss, acc = replay()
+        return True, loss, acc, 0.0
 
     # -- batched CDF timing for the graph path -------------------------
     def _cdf_event_pair(self):
@@ -346,6 +395,13 @@ class Trainer:
             self.step = step0
             if self.is_chief:
                 log.info("Restored checkpoint at step %d", step0)
+        resident = isinstance(dataset, DeviceDataSet)
+        if resident:
+            if self._resident_ds is not dataset:
+                self.attach_dataset(dataset)
+            # the batch sequence is a function of the step: a resumed run
+            # continues exactly where the uninterrupted one would be
+            dataset.seek(self.step)
         time_acc_list = []
         begin_time = time.time()
         writer = None
@@ -355,8 +411,14 @@ class Trainer:
         next_summary_time = time.time() + flags.save_summaries_secs
         while self.step < max_steps:
             start_time = time.time()
-            images, labels = dataset.next_batch(flags.batch_size)
-            images, labels = self.to_device(images, labels)
+            if resident:
+                images = labels = None
+                if flags.timeline_logging and 5 <= self.step <= 7:
+                    images, labels = dataset.batch_at(self.step,
+                                                      flags.batch_size)
+            else:
+                images, labels = dataset.next_batch(flags.batch_size)
+                images, labels = self.to_device(images, labels)
             if flags.timeline_logging and 5 <= self.step <= 7:
                 # chrome trace per step (reference FULL_TRACE timelines,
                 # distributed_train.py:317-358) via torch.profiler/kineto
@@ -371,6 +433,9 @@ class Trainer:
                 prof.export_chrome_trace(os.path.join(
                     flags.train_dir,
                     f"worker={self.rank}_timeline_iter={self.step}.json"))
+                finish_time = time.time()
+            elif resident:
+                applied, loss_v, acc_v, _ct = self.resident_step()
                 finish_time = time.time()
             else:
                 applied, loss_v, acc_v, _ct = self.graph_or_eager_step(images, labels)
@@ -428,6 +493,18 @@ class Trainer:
 
 
 def make_dataset(flags, rank: int, world: int, device, dtype):
+    device_data = getattr(flags, "device_data", False)
+    if device_data and (flags.synthetic_data or flags.fake_data):
+        log.info("--device_data has no effect with --synthetic_data / "
+                 "--fake_data")
+        device_data = False
+    if device_data:
+        from ..data import load_device_mnist
+        return load_device_mnist(flags.data_dir, subset=flags.subset,
+                                 worker_id=rank, n_workers=world,
+                                 shard=not flags.no_shard,
+                                 seed=flags.seed + rank, device=device,
+                                 dtype=dtype)
     if flags.synthetic_data:
         pool = max(4 * flags.batch_size, 8192)
         return SyntheticDataSet(pool_size=pool, device=device, dtype=dtype,

@@ -184,3 +184,83 @@ def sgd_step(master, grad, lr: float, grad_scale: float = 1.0,
     if shadow is not None:
         shadow.copy_(master.to(shadow.dtype))
     return master
+
+
+# ---------------------------------------------------------------------------
+# Device-resident input pipeline: stateless epoch permutation + batch gather.
+# Bit-exact oracle of csrc/data_gather.hip (and the CPU / fp32-on-GPU path).
+# All permutation arithmetic is unsigned mod 2^32.
+# ---------------------------------------------------------------------------
+
+_M32 = 0xFFFFFFFF
+
+
+def _mix32(x):
+    """murmur3 finalizer on python ints or uint64 numpy arrays (values kept
+    below 2^32, so the 64-bit products never overflow before masking)."""
+    x = x ^ (x >> 16)
+    x = (x * 0x85EBCA6B) & _M32
+    x = x ^ (x >> 13)
+    x = (x * 0xC2B2AE35) & _M32
+    return x ^ (x >> 16)
+
+
+def feistel_perm(n: int, seed: int, epoch: int, p):
+    """Cycle-walking 4-round Feistel permutation of [0, n) keyed on
+    (64-bit seed, epoch).  p: int array of positions in [0, n) -> int64
+    array of sample indices.  Epoch 0 is the identity (first epoch
+    unshuffled, as data/mnist_data.py DataSet)."""
+    import numpy as np
+    p = np.asarray(p, dtype=np.int64)
+    if p.size and not (0 <= p.min() and p.max() < n):
+        raise ValueError(f"positions must lie in [0, {n})")
+    if epoch == 0:
+        return p.copy()
+    seed &= 0xFFFFFFFFFFFFFFFF
+    base = _mix32((seed & _M32) ^ _mix32(((seed >> 32) + 0x9E3779B9) & _M32))
+    keys = [_mix32((base + (epoch & _M32) * 0x9E3779B1 + r) & _M32)
+            for r in range(4)]
+    bits = max(2, (n - 1).bit_length())
+    bits += bits & 1
+    h = np.uint64(bits // 2)
+    mask = np.uint64((1 << (bits // 2)) - 1)
+    m32 = np.uint64(_M32)
+
+    def enc(v):
+        L, R = v >> h, v & mask
+        for k in keys:
+            f = _mix32((R * np.uint64(0x9E3779B1) + np.uint64(k)) & m32)
+            L, R = R, L ^ (f & mask)
+        return (L << h) | R
+
+    v = enc(p.astype(np.uint64))
+    out = v >= np.uint64(n)
+    while out.any():
+        v[out] = enc(v[out])
+        out = v >= np.uint64(n)
+    return v.astype(np.int64)
+
+
+def batch_indices(n: int, batch_size: int, seed: int, step: int):
+    """Sample indices of the batch at `step`: spe = n // B batches per epoch
+    (the n % B tail is dropped, as DataSet.next_batch drops it), epoch =
+    step // spe, sample j = perm(epoch, (step % spe) * B + j)."""
+    import numpy as np
+    if not 1 <= batch_size <= n:
+        raise ValueError(f"batch size {batch_size} must be in [1, N={n}]")
+    if step < 0:
+        raise ValueError("step must be >= 0")
+    spe = n // batch_size
+    epoch, pos = divmod(int(step), spe)
+    p = pos * batch_size + np.arange(batch_size, dtype=np.int64)
+    return feistel_perm(n, seed, epoch, p)
+
+
+def batch_gather(img_u8, lab_u8, lut, x, y, seed: int, step: int):
+    """x[j] = lut[img_u8[idx[j]]], y[j] = lab_u8[idx[j]] written into the
+    caller's buffers (any device; x takes lut's dtype)."""
+    n, b = lab_u8.shape[0], y.shape[0]
+    idx = torch.from_numpy(batch_indices(n, b, seed, step)).to(img_u8.device)
+    x.copy_(lut[img_u8[idx].long()].reshape(x.shape))
+    y.copy_(lab_u8[idx].long())
+    return x, y

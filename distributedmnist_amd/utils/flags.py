@@ -86,6 +86,12 @@ def build_train_parser() -> argparse.ArgumentParser:
                         "AGGREGATED gradient (default is the reference's "
                         "per-worker pre-aggregation masks, "
                         "distributed_train.py:194-203)")
+    p.add_argument("--device_data", action="store_true",
+                   help="keep the idx-gz training set on the device as uint8 "
+                        "and gather each batch there (inside the hipGraph "
+                        "when the step is captured); the batch order is a "
+                        "pure function of (seed, rank, step). No effect "
+                        "with --synthetic_data / --fake_data")
     return p
 
 
