@@ -248,8 +248,17 @@ std::vector<torch::Tensor> conv_pool_fwd(torch::Tensor x, torch::Tensor w,
   p.CB = NB; p.CH = H; p.CW = W; p.CHo = Ho; p.CWo = Wo;
   p.Cin = Cin; p.Cout = Cout;
   auto s = cur_stream();
-  if (Cin == 1) {
-    // direct VALU kernel: K=25 is too small for MFMA to win here
+  if (Cin == 1 && conv1_mfma_supported(H, W, Cin, Cout) &&
+      conv1_mfma_enabled() &&
+      reinterpret_cast<uintptr_t>(x.data_ptr()) % 8 == 0) {
+    // LeNet conv1: per-image LDS slab feeding 32x32x16 MFMAs with
+    // contiguous-pixel A fragments (conv1_mfma.hip)
+    launch_conv1_mfma_fwd(bf16_ptr(x), bf16_ptr(w), b.data_ptr<float>(),
+                          bf16_mut(y), amax.data_ptr<uint8_t>(), NB, s);
+  } else if (Cin == 1) {
+    // other Cin=1 shapes (and DMNIST_CONV1_VALU=1): direct v_dot2c kernel.
+    // The im2col MFMA form loses here (per-element global A gather,
+    // 579 us at B=8192); only the slab form above beats the VALU kernel.
     launch_conv1_direct_fwd(bf16_ptr(x), bf16_ptr(w), b.data_ptr<float>(),
                             bf16_mut(y), amax.data_ptr<uint8_t>(), NB, H, W,
                             Cout, s);
@@ -558,6 +567,15 @@ void conv1_dw_pooled(torch::Tensor x, torch::Tensor dyp, torch::Tensor am,
   TORCH_CHECK(x.size(3) == 1 && H == 28 && W == 28 && Cout == 32 &&
                   dyp.size(1) == H / 2 && dyp.size(2) == W / 2,
               "conv1_dw_pooled: LeNet conv1 shapes only");
+  CHECK_CONTIG(am); CHECK_F32(dw_out); CHECK_CONTIG(dw_out);
+  if (conv1_mfma_supported(H, W, 1, Cout) && conv1_mfma_enabled() &&
+      reinterpret_cast<uintptr_t>(x.data_ptr()) % 8 == 0) {
+    launch_conv1_mfma_dw(bf16_ptr(x), bf16_ptr(dyp), am.data_ptr<uint8_t>(),
+                         dw_out.data_ptr<float>(),
+                         db_out.defined() ? db_out.data_ptr<float>() : nullptr,
+                         NB, cur_stream());
+    return;
+  }
   launch_conv1_dw_pooled(bf16_ptr(x), bf16_ptr(dyp),
                          am.data_ptr<uint8_t>(), dw_out.data_ptr<float>(),
                          db_out.defined() ? db_out.data_ptr<float>() : nullptr,
@@ -601,14 +619,32 @@ std::vector<torch::Tensor> softmax_xent_fwd(torch::Tensor logits,
   CHECK_CONTIG(labels);
   int B = logits.size(0), C = logits.size(1);
   TORCH_CHECK(C <= 16, "softmax_xent kernel supports C<=16");
+  TORCH_CHECK(B <= 256 * SOFTMAX_MAX_BLOCKS, "softmax_xent: batch too large");
   auto dl = torch::empty_like(logits);
-  auto out = torch::zeros({2}, logits.options().dtype(at::kFloat));
+  // the kernel STORES both outputs (last-block reduction), so no zero-fill
+  // launch per step.  Its workspace (per-block partials + ticket counter)
+  // is allocated and zeroed once per device; the counter resets itself.
+  auto out = torch::empty({2}, logits.options().dtype(at::kFloat));
+  static std::vector<torch::Tensor>* ws = new std::vector<torch::Tensor>(64);
+  int dev = logits.get_device();
+  TORCH_CHECK(dev >= 0 && dev < 64, "softmax_xent: bad device index");
+  if (!(*ws)[dev].defined()) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    hipStreamIsCapturing(cur_stream(), &cap);
+    TORCH_CHECK(cap == hipStreamCaptureStatusNone,
+                "softmax_xent_fwd: first call on a device allocates its "
+                "workspace and must run outside graph capture");
+    (*ws)[dev] = torch::zeros({2 * SOFTMAX_MAX_BLOCKS + 1},
+                              logits.options().dtype(at::kFloat));
+  }
+  float* part = (*ws)[dev].data_ptr<float>();
+  unsigned* ticket = reinterpret_cast<unsigned*>(part + 2 * SOFTMAX_MAX_BLOCKS);
   float* dbp = nullptr;
   if (db_out.has_value() && db_out->defined())
     dbp = db_out->data_ptr<float>();
   launch_softmax_xent(bf16_ptr(logits), labels.data_ptr<long>(),
                       bf16_mut(dl), out.data_ptr<float>(), B, C, dbp,
-                      (float)inv_n, cur_stream());
+                      (float)inv_n, part, ticket, cur_stream());
   auto loss = out.select(0, 0);
   auto correct = out.select(0, 1);
   return {loss, correct, dl};
@@ -792,6 +828,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "conv1 dW+db from the pooled gradient (pool bwd fused, no dact1)",
         py::arg("x"), py::arg("dyp"), py::arg("am"),
         py::arg("dw_out"), py::arg("db_out"));
+  m.def("conv1_dw_group", [](int64_t NB) {
+          return (int64_t)conv1_mfma_dw_group((int)NB);
+        }, "images per block the MFMA conv1 dW launcher picks for batch NB");
   m.def("conv_dx", &conv_dx, "conv dX");
   m.def("linear_act_bwd", &linear_act_bwd, "linear backward (dx, dw, db)");
   m.def("linear_act_bwd_into", &linear_act_bwd_into,

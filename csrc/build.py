@@ -24,7 +24,8 @@ def main():
     abi = int(torch.compiled_with_cxx11_abi())
 
     srcs = [os.path.join(ROOT, f) for f in
-            ("gemm_tile.hip", "conv_slab.hip", "dw_tr.hip", "ops_misc.hip", "data_gather.hip",
+            ("gemm_tile.hip", "conv_slab.hip", "dw_tr.hip", "ops_misc.hip", "conv1_mfma.hip",
+             "data_gather.hip",
              "bindings.cpp")]
     out = os.path.join(ROOT, "_dmnist_hip.so")
 

@@ -53,9 +53,13 @@ void launch_pool_bwd_scatter(const unsigned short* dy, const unsigned short* y,
                              const uint8_t* amax, unsigned short* dact,
                              float* db, int Mpool, int C, int H, int W, int Wo,
                              hipStream_t);
+// out[2] is stored (no pre-zeroing); part/ticket: persistent workspace of
+// 2*SOFTMAX_MAX_BLOCKS floats + one zero-initialised, self-resetting counter
+#define SOFTMAX_MAX_BLOCKS 4096
 void launch_softmax_xent(const unsigned short* logits, const long* labels,
                          unsigned short* dlogits, float* out, int B, int C,
-                         float* db, float inv_n, hipStream_t);
+                         float* db, float inv_n, float* part,
+                         unsigned* ticket, hipStream_t);
 void launch_sgd_step(float* master, float* grad, unsigned short* shadow,
                      int has_shadow, long n, float lr_scale, float dc_keep,
                      uint64_t seed, uint64_t offset, float* momentum, float mu,
@@ -138,6 +142,18 @@ void launch_conv1_dw_slab(const unsigned short* x, const unsigned short* dact,
 void launch_conv1_dw_direct(const unsigned short* x,
                             const unsigned short* dact, float* dw, int NB,
                             int H, int W, int Cout, hipStream_t s);
+// conv1_mfma.hip — LeNet conv1 (28x28, Cin=1, Cout=32) fwd and pooled dW on
+// v_mfma_f32_32x32x16_bf16; DMNIST_CONV1_VALU=1 (read per call) forces the
+// v_dot2c kernels above
+bool conv1_mfma_supported(int H, int W, int Cin, int Cout);
+bool conv1_mfma_enabled();
+int conv1_mfma_dw_group(int NB);  // images per block the dW launcher picks
+void launch_conv1_mfma_fwd(const unsigned short* x, const unsigned short* w,
+                           const float* bias, unsigned short* y,
+                           uint8_t* amax, int NB, hipStream_t);
+void launch_conv1_mfma_dw(const unsigned short* x, const unsigned short* dyp,
+                          const uint8_t* am, float* dw, float* db, int NB,
+                          hipStream_t);
 // gemm_tile.hip — split-K fwd slice entries + their summing epilogue
 void gemm_fwd_slices_64(const GemmParams&, hipStream_t);
 void gemm_fwd_slices_64_bt(const GemmParams&, hipStream_t);

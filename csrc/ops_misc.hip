@@ -2,7 +2,9 @@
 // sums), maxpool backward scatter (+ conv bias grad), fused softmax-CE
 // (+top-1 correct count), the fused flat SGD apply (+drop-connect mask,
 // + bf16 shadow refresh), bf16 transpose, and the Cin=1 conv layer's
-// direct v_dot2c_f32_bf16 forward/dW (K=25 is below MFMA's win threshold).
+// direct v_dot2c_f32_bf16 forward/dW.  The LeNet conv1 shape itself now runs
+// on MFMA (conv1_mfma.hip); these serve every other Cin=1 shape and the
+// DMNIST_CONV1_VALU=1 A/B override.
 
 #include "common.h"
 #include "kernels.h"
@@ -125,14 +127,21 @@ void pool_bwd_scatter_kernel(const ushort_t* dy, const ushort_t* y,
 
 // ---------------------------------------------------------------------------
 // Fused softmax cross-entropy fwd(+grad) + top-1 correct count.
-// One thread per row (C <= 16); out[0] += sum(loss)/B ; out[1] += correct.
+// One thread per row (C <= 16); out[0] = sum(loss)/B ; out[1] = correct.
 // dlogits = (softmax - onehot)/B, bf16.
+// out is STORED, never accumulated into, so the caller needs no zero-fill
+// launch: every block parks its two partials in `part`, takes a ticket, and
+// the last block to arrive sums the partials in block order (deterministic)
+// and stores the result.  The ticket counter resets itself; `part`/`ticket`
+// are one persistent workspace per device, so launches on one device must
+// not overlap (they never do: one softmax per training step).
 // ---------------------------------------------------------------------------
 template <int CC>
 __global__ __launch_bounds__(256)
 void softmax_xent_t_kernel(const ushort_t* logits, const long* labels,
                            ushort_t* dlogits, float* out, int B, int C,
-                           float* db, float inv_n) {
+                           float* db, float inv_n, float* part,
+                           unsigned* ticket) {
   // CC > 0: compile-time class count — every per-class loop unrolls and
   // v[] lives in REGISTERS.  The runtime-C form kept v[16] in scratch
   // (runtime-indexed array): measured 30 us at B=1024 vs ~5 with CC=10.
@@ -141,9 +150,8 @@ void softmax_xent_t_kernel(const ushort_t* logits, const long* labels,
   // naive per-thread LDS atomics serialized 64-way).
   // inv_n: out[1] += correct * inv_n (1/B = accuracy mean in-kernel).
   if (CC) C = CC;
-  __shared__ float red[2];
+  __shared__ float wred[4][2];  // per-wave (loss, correct) partials
   __shared__ float dbred[16];
-  if (threadIdx.x == 0) { red[0] = 0.f; red[1] = 0.f; }
   if (db && threadIdx.x < 16) dbred[threadIdx.x] = 0.f;
   __syncthreads();
   int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -209,8 +217,20 @@ void softmax_xent_t_kernel(const ushort_t* logits, const long* labels,
       correct = (arg == (int)lab) ? 1.f : 0.f;
     }
   }
-  atomicAdd(&red[0], loss);
-  atomicAdd(&red[1], correct * inv_n);
+  {
+    // shuffle tree + fixed-order sums: loss/accuracy are bitwise
+    // reproducible from launch to launch (no float atomics on their path)
+    float ls = loss, cs = correct * inv_n;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      ls += __shfl_down(ls, off, 64);
+      cs += __shfl_down(cs, off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+      wred[threadIdx.x >> 6][0] = ls;
+      wred[threadIdx.x >> 6][1] = cs;
+    }
+  }
   if (db) {
 #pragma unroll
     for (int c = 0; c < (CC ? CC : 16); ++c) {
@@ -225,13 +245,41 @@ void softmax_xent_t_kernel(const ushort_t* logits, const long* labels,
     }
   }
   __syncthreads();
-  if (threadIdx.x == 0) {
-    atomicAdd(&out[0], red[0]);
-    atomicAdd(&out[1], red[1]);
-  }
   if (db && (int)threadIdx.x < C) {
     float v2 = dbred[threadIdx.x];
     if (v2 != 0.f) atomicAdd(&db[threadIdx.x], v2);
+  }
+  if (threadIdx.x == 0) {
+    const unsigned nblk = gridDim.x;
+    float r0 = 0.f, r1 = 0.f;
+    for (unsigned wv = 0; wv < (blockDim.x + 63) / 64; ++wv) {
+      r0 += wred[wv][0];
+      r1 += wred[wv][1];
+    }
+    if (nblk == 1) {
+      out[0] = r0;
+      out[1] = r1;
+    } else {
+      __hip_atomic_store(&part[2 * blockIdx.x], r0, __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&part[2 * blockIdx.x + 1], r1, __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_AGENT);
+      __threadfence();  // partials visible device-wide before the ticket
+      if (atomicAdd(ticket, 1u) == nblk - 1) {
+        __threadfence();
+        float s0 = 0.f, s1 = 0.f;
+        for (unsigned i = 0; i < nblk; ++i) {
+          s0 += __hip_atomic_load(&part[2 * i], __ATOMIC_RELAXED,
+                                  __HIP_MEMORY_SCOPE_AGENT);
+          s1 += __hip_atomic_load(&part[2 * i + 1], __ATOMIC_RELAXED,
+                                  __HIP_MEMORY_SCOPE_AGENT);
+        }
+        out[0] = s0;
+        out[1] = s1;
+        __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
   }
 }
 
@@ -405,18 +453,24 @@ void launch_pool_bwd_scatter(const unsigned short* dy, const unsigned short* y,
 
 void launch_softmax_xent(const unsigned short* logits, const long* labels,
                          unsigned short* dlogits, float* out, int B, int C,
-                         float* db, float inv_n, hipStream_t s) {
+                         float* db, float inv_n, float* part,
+                         unsigned* ticket, hipStream_t s) {
   // one row per thread: B=1024 in 256-thread blocks was only 4 blocks
   // (256-CU chip ~idle) — 64-thread blocks spread it; at large B the
-  // extra per-block out[] atomics cost more than the spread gains
+  // last block's serial sum over the per-block partials costs more than
+  // the spread gains.  The grid never exceeds SOFTMAX_MAX_BLOCKS (the
+  // workspace holds two partials per block).
   int bt = B >= 2048 ? 256 : 64;
+  if (cdivh(B, bt) > SOFTMAX_MAX_BLOCKS) bt = 256;
   dim3 grid(cdivh(B, bt));
   if (C == 10)
     hipLaunchKernelGGL((softmax_xent_t_kernel<10>), grid, dim3(bt), 0, s,
-                       logits, labels, dlogits, out, B, C, db, inv_n);
+                       logits, labels, dlogits, out, B, C, db, inv_n, part,
+                       ticket);
   else
     hipLaunchKernelGGL((softmax_xent_t_kernel<0>), grid, dim3(bt), 0, s,
-                       logits, labels, dlogits, out, B, C, db, inv_n);
+                       logits, labels, dlogits, out, B, C, db, inv_n, part,
+                       ticket);
 }
 
 void launch_sgd_step(float* master, float* grad, unsigned short* shadow,
@@ -536,9 +590,12 @@ void transpose_bf16_kernel(const ushort_t* src, ushort_t* dst, int R, int C) {
 
 // ---------------------------------------------------------------------------
 // Direct conv1 fwd (Cin==1): fused 5x5 conv + bias + ReLU + maxpool2x2.
-// K=25 is too small for MFMA to win (<=25/32 K-utilization plus a scalar
-// im2col gather) — a VALU kernel with LDS-staged windows/weights is ~9x
-// faster than the implicit-GEMM form at B=8192 (measured 579us -> VALU).
+// Against the im2col implicit-GEMM MFMA form (<=25/32 K-utilization plus a
+// per-element global A gather) this VALU kernel with LDS-staged
+// windows/weights is ~9x faster at B=8192 (measured 579us -> VALU, round 1).
+// That comparison does not cover an LDS-slab MFMA form whose K axis is 8
+// contiguous slab pixels per lane: conv1_mfma.hip, which replaced this
+// kernel for the 28x28x1->32 shape (38 -> 15 us solo at B=1024).
 // Block: 256 threads = 8 pooled pixels x 32 Cout; each thread does
 // 4 conv positions x 25 MACs fp32 from LDS broadcasts.
 // ---------------------------------------------------------------------------
@@ -548,8 +605,8 @@ void conv1_direct_fwd_kernel(const ushort_t* x, const ushort_t* w,
                              int NB, int H, int W, int Cout, int Mpool) {
   // One IMAGE per block (H=W=28): x staged once as a PACKED bf16 [32][32]
   // padded slab (2 KB); 256 threads = 32 co x 8 slots, each slot walking a
-  // CONTIGUOUS run of pooled pixels.  K=25 with Cin=1 is too small for
-  // MFMA; the math runs on v_dot2c_f32_bf16 (2 MACs/op): the 6-column
+  // CONTIGUOUS run of pooled pixels.  The math runs on v_dot2c_f32_bf16
+  // (2 MACs/op): the 6-column
   // window is held as 3 even-aligned bf16 PAIRS per row (one ds_read_b32
   // each), odd-based pixels read the cross pairs built with one
   // v_alignbit, and the kw=4 tail is a dot2 against a zero-padded tap
@@ -712,8 +769,9 @@ void launch_conv1_direct_fwd(const unsigned short* x, const unsigned short* w,
 // ---------------------------------------------------------------------------
 // conv1 backward dW, direct VALU form (Cin == 1, K = 25 taps).
 // dw[kh][kw][co] = sum_{n,h,w} x[n, h+kh-2, w+kw-2] * dact[n,h,w,co].
-// MFMA loses at K=25 (M-util 25/32 and the A gather is per-element); here
-// each lane owns one co and 25 fp32 accumulators; the x image is staged once
+// The im2col MFMA form loses at K=25 (M-util 25/32 and a per-element global
+// A gather; the slab MFMA form of conv1_mfma.hip is a different design and
+// wins for the pooled LeNet shape); here each lane owns one co and 25 fp32 accumulators; the x image is staged once
 // per block as the same padded fp32 [32][32] slab the conv1 forward uses,
 // and the 5x5 x-window walks each row with a 5-phase cyclic column buffer —
 // 5 broadcast LDS reads + 25 v_fmac per pixel.  A block accumulates G

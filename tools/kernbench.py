@@ -80,7 +80,7 @@ def bench_batch(ext, B):
     shadow = torch.zeros(1663370, dtype=bf16, device=dev)
 
     rows = [
-        ("conv1 fwd (direct VALU slab)", lambda: ext.conv_pool_fwd(x1, w1, b1, None)),
+        ("conv1 fwd (MFMA slab; DMNIST_CONV1_VALU=1: dot2 VALU)", lambda: ext.conv_pool_fwd(x1, w1, b1, None)),
         ("conv2 fwd (MFMA image slab)", lambda: ext.conv_pool_fwd(y1, w2, b2, w2T)),
         ("fc1 fwd+relu+dropout (MFMA, wT)", lambda: ext.linear_act_fwd(h2, f1, fb1, True, 0.5, 1, 2, wT=f1T)),
         ("fc2 fwd (MFMA, wT)", lambda: ext.linear_act_fwd(a1, f2, fb2, False, 1.0, 0, 0, wT=f2T)),
@@ -98,8 +98,8 @@ def bench_batch(ext, B):
         ("conv2 dW (slab/gemm tiered)", lambda: ext.conv_dw_into(y1, dact2, dwc2)),
         ("conv2 dX (image slab)", lambda: ext.conv_dx(dact2, w2, 32)),
         ("pool1 bwd scatter", lambda: ext.pool_scatter(dxc, y1, am1, dbc1, 28, 28)),
-        ("conv1 dW (slab)", lambda: ext.conv_dw_into(x1, dact1, dwc1)),
-        ("conv1 dW+db pooled fused", lambda: ext.conv1_dw_pooled(x1, dxc, am1, dwc1.view(-1), dbc1)),
+        ("conv1 dW from dact (direct dot2 VALU)", lambda: ext.conv_dw_into(x1, dact1, dwc1)),
+        ("conv1 dW+db pooled fused (MFMA; DMNIST_CONV1_VALU=1: dot2 VALU)", lambda: ext.conv1_dw_pooled(x1, dxc, am1, dwc1.view(-1), dbc1)),
         ("fused SGD apply (1.66M params)", lambda: ext.sgd_step(master, grad, shadow, True, 0.01, 1.0, -1.0, 0, 0)),
     ]
     print(f"\n## B = {B} (solo, median of 30, us)\n")
