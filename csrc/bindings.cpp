@@ -46,6 +46,14 @@ int dw_tr_level() {
 }
 bool dw_tr_enabled() { return dw_tr_level() != 0; }
 
+// conv2 dW from pixel-major LDS slabs (conv2_dw_slab.hip) replaces
+// conv_dw_tr for its one shape; DMNIST_DW2_SLAB=0 (read per call) and the
+// DMNIST_DW_SPREAD contention probe keep conv_dw_tr
+bool conv2_dw_slab_route(int H, int W, int Cin, int Cout) {
+  return conv2_dw_slab_supported(H, W, Cin, Cout) && dw_tr_enabled() &&
+         conv2_dw_slab_enabled() && !getenv("DMNIST_DW_SPREAD");
+}
+
 // --------------------------------------------------------------------------
 torch::Tensor linear_act_fwd_impl(torch::Tensor x, torch::Tensor w,
                                   torch::Tensor b, bool relu, double p_keep,
@@ -328,6 +336,9 @@ std::vector<torch::Tensor> conv_pool_bwd_impl(torch::Tensor dy, torch::Tensor x,
       // >=4 images/block; below that the implicit-GEMM form is faster
       launch_conv_dw_slab(bf16_ptr(x), bf16_ptr(dact), dw.data_ptr<float>(),
                           NB, H, W, Cin, Cout, s);
+    } else if (conv2_dw_slab_route(H, W, Cin, Cout)) {
+      launch_conv2_dw_slab(bf16_ptr(x), bf16_ptr(dact), dw.data_ptr<float>(),
+                           NB, s);
     } else {
       int tiles = cdiv(p.M, 128) * cdiv(p.N, 64);
       // total blocks target (DMNIST_DW_BLOCKS sweeps it): at BK=32 the
@@ -531,6 +542,9 @@ void conv_dw_into(torch::Tensor x, torch::Tensor dact, torch::Tensor dw_out) {
              ((dw_tr_level() == 0 && NB >= 2048) || getenv("DMNIST_DW_G"))) {
     launch_conv_dw_slab(bf16_ptr(x), bf16_ptr(dact), dw_out.data_ptr<float>(),
                         NB, H, W, Cin, Cout, s);
+  } else if (conv2_dw_slab_route(H, W, Cin, Cout)) {
+    launch_conv2_dw_slab(bf16_ptr(x), bf16_ptr(dact),
+                         dw_out.data_ptr<float>(), NB, s);
   } else {
     int tiles = cdiv(p.M, 128) * cdiv(p.N, 64);
     // total blocks target (DMNIST_DW_BLOCKS sweeps it): at BK=32 the
@@ -831,6 +845,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv1_dw_group", [](int64_t NB) {
           return (int64_t)conv1_mfma_dw_group((int)NB);
         }, "images per block the MFMA conv1 dW launcher picks for batch NB");
+  m.def("conv2_dw_group", [](int64_t NB) {
+          return (int64_t)conv2_dw_group((int)NB);
+        }, "images per block the slab conv2 dW launcher picks for batch NB");
   m.def("conv_dx", &conv_dx, "conv dX");
   m.def("linear_act_bwd", &linear_act_bwd, "linear backward (dx, dw, db)");
   m.def("linear_act_bwd_into", &linear_act_bwd_into,

@@ -154,6 +154,14 @@ void launch_conv1_mfma_fwd(const unsigned short* x, const unsigned short* w,
 void launch_conv1_mfma_dw(const unsigned short* x, const unsigned short* dyp,
                           const uint8_t* am, float* dw, float* db, int NB,
                           hipStream_t);
+// conv2_dw_slab.hip — LeNet conv2 dW (14x14, Cin=32, Cout=64) from pixel-
+// major per-image LDS slabs (glds + tr16); DMNIST_DW2_SLAB=0 (read per call)
+// routes the shape back to conv_dw_tr
+bool conv2_dw_slab_supported(int H, int W, int Cin, int Cout);
+bool conv2_dw_slab_enabled();
+int conv2_dw_group(int NB);  // images per block the launcher picks
+void launch_conv2_dw_slab(const unsigned short* x, const unsigned short* dact,
+                          float* dw, int NB, hipStream_t);
 // gemm_tile.hip — split-K fwd slice entries + their summing epilogue
 void gemm_fwd_slices_64(const GemmParams&, hipStream_t);
 void gemm_fwd_slices_64_bt(const GemmParams&, hipStream_t);
