@@ -813,6 +813,104 @@ void batch_gather(torch::Tensor img_u8, torch::Tensor lab_u8,
                       (uint64_t)step, sd, cur_stream());
 }
 
+void range_gather(torch::Tensor img_u8, torch::Tensor lab_u8,
+                  torch::Tensor lut, torch::Tensor x, torch::Tensor y,
+                  int64_t start, c10::optional<torch::Tensor> start_dev) {
+  CHECK_CUDA(img_u8); CHECK_CONTIG(img_u8);
+  CHECK_CUDA(lab_u8); CHECK_CONTIG(lab_u8);
+  CHECK_CUDA(lut); CHECK_BF16(lut); CHECK_CONTIG(lut);
+  CHECK_CUDA(x); CHECK_BF16(x); CHECK_CONTIG(x);
+  CHECK_CUDA(y); CHECK_CONTIG(y);
+  TORCH_CHECK(img_u8.scalar_type() == at::kByte &&
+              lab_u8.scalar_type() == at::kByte,
+              "range_gather: images/labels must be uint8");
+  TORCH_CHECK(y.scalar_type() == at::kLong, "range_gather: y must be int64");
+  const int64_t N = lab_u8.numel(), B = y.numel();
+  TORCH_CHECK(N >= 1 && N < (int64_t(1) << 31),
+              "range_gather: N out of range");
+  // B > N is legal here: the rows past N are padding
+  TORCH_CHECK(B >= 1 && B < (int64_t(1) << 31),
+              "range_gather: chunk size out of range");
+  TORCH_CHECK(img_u8.numel() == N * 784, "range_gather: images must be [N,784]");
+  TORCH_CHECK(x.numel() == B * 784, "range_gather: x must hold B*784 values");
+  TORCH_CHECK(lut.numel() == 256, "range_gather: lut must have 256 entries");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(img_u8.data_ptr()) % 8 == 0 &&
+              reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "range_gather: images must be 8B- and x 16B-aligned");
+  const long* sd = nullptr;
+  if (start_dev.has_value() && start_dev->defined()) {
+    TORCH_CHECK(start_dev->is_cuda() && start_dev->scalar_type() == at::kLong &&
+                start_dev->numel() >= 1, "range_gather: start_dev must be a "
+                "device int64 tensor");
+    sd = start_dev->data_ptr<long>();
+  } else {
+    TORCH_CHECK(start >= 0, "range_gather: start must be >= 0");
+  }
+  launch_range_gather(img_u8.data_ptr<uint8_t>(), lab_u8.data_ptr<uint8_t>(),
+                      bf16_ptr(lut), bf16_mut(x), y.data_ptr<long>(),
+                      (uint32_t)N, (uint32_t)B, (uint64_t)start, sd,
+                      cur_stream());
+}
+
+void softmax_eval(torch::Tensor logits, torch::Tensor labels,
+                  torch::Tensor loss_sum, torch::Tensor counts,
+                  c10::optional<torch::Tensor> pred,
+                  c10::optional<torch::Tensor> cursor_dev) {
+  CHECK_CUDA(logits); CHECK_BF16(logits); CHECK_CONTIG(logits);
+  CHECK_CUDA(labels); CHECK_CONTIG(labels);
+  CHECK_CUDA(loss_sum); CHECK_F32(loss_sum); CHECK_CONTIG(loss_sum);
+  CHECK_CUDA(counts); CHECK_CONTIG(counts);
+  TORCH_CHECK(logits.dim() == 2, "softmax_eval: logits must be [B,C]");
+  TORCH_CHECK(labels.scalar_type() == at::kLong,
+              "softmax_eval: labels must be int64");
+  TORCH_CHECK(counts.scalar_type() == at::kInt,
+              "softmax_eval: counts must be int32");
+  const int64_t B = logits.size(0), C = logits.size(1);
+  TORCH_CHECK(C >= 1 && C <= 16, "softmax_eval kernel supports 1<=C<=16");
+  TORCH_CHECK(B >= 1 && B <= 256 * SOFTMAX_MAX_BLOCKS,
+              "softmax_eval: batch out of range");
+  TORCH_CHECK(labels.numel() == B, "softmax_eval: labels must be [B]");
+  TORCH_CHECK(loss_sum.numel() >= 1, "softmax_eval: loss_sum must be [1]");
+  TORCH_CHECK(counts.numel() == 2 + C * C,
+              "softmax_eval: counts must hold 2 + C*C = ", 2 + C * C,
+              " values");
+  uint8_t* pp = nullptr;
+  if (pred.has_value() && pred->defined()) {
+    TORCH_CHECK(pred->is_cuda() && pred->scalar_type() == at::kByte &&
+                pred->is_contiguous() && pred->numel() == B,
+                "softmax_eval: pred must be a contiguous device uint8 [B]");
+    pp = pred->data_ptr<uint8_t>();
+  }
+  long* cp = nullptr;
+  if (cursor_dev.has_value() && cursor_dev->defined()) {
+    TORCH_CHECK(cursor_dev->is_cuda() &&
+                cursor_dev->scalar_type() == at::kLong &&
+                cursor_dev->numel() >= 1, "softmax_eval: cursor_dev must be "
+                "a device int64 tensor");
+    cp = cursor_dev->data_ptr<long>();
+  }
+  // the kernel's own partial/ticket workspace (never the training
+  // softmax's), allocated and zeroed once per device; the counter resets
+  // itself
+  static std::vector<torch::Tensor>* ws = new std::vector<torch::Tensor>(64);
+  int dev = logits.get_device();
+  TORCH_CHECK(dev >= 0 && dev < 64, "softmax_eval: bad device index");
+  if (!(*ws)[dev].defined()) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    hipStreamIsCapturing(cur_stream(), &cap);
+    TORCH_CHECK(cap == hipStreamCaptureStatusNone,
+                "softmax_eval: first call on a device allocates its "
+                "workspace and must run outside graph capture");
+    (*ws)[dev] = torch::zeros({SOFTMAX_MAX_BLOCKS + 1},
+                              logits.options().dtype(at::kFloat));
+  }
+  float* part = (*ws)[dev].data_ptr<float>();
+  unsigned* ticket = reinterpret_cast<unsigned*>(part + SOFTMAX_MAX_BLOCKS);
+  launch_softmax_eval(bf16_ptr(logits), labels.data_ptr<long>(),
+                      loss_sum.data_ptr<float>(), counts.data_ptr<int>(), pp,
+                      cp, (int)B, (int)C, part, ticket, cur_stream());
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -888,6 +986,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("img_u8"), py::arg("lab_u8"), py::arg("lut"), py::arg("x"),
         py::arg("y"), py::arg("seed"), py::arg("step"),
         py::arg("step_dev") = c10::nullopt);
+  m.def("range_gather", &range_gather,
+        "sequential chunk [start, start+B) of the device-resident uint8 set "
+        "(LUT-normalised to bf16) into x [B,28,28,1] bf16 / y [B] int64; "
+        "rows past N are zero-filled with label -1",
+        py::arg("img_u8"), py::arg("lab_u8"), py::arg("lut"), py::arg("x"),
+        py::arg("y"), py::arg("start"),
+        py::arg("start_dev") = c10::nullopt);
+  m.def("softmax_eval", &softmax_eval,
+        "evaluation statistics accumulated across launches: loss_sum[1] "
+        "fp32, counts[2 + C*C] int32 (live, correct, confusion), optional "
+        "pred[B] uint8 and cursor_dev += B; rows with a label outside "
+        "[0, C) contribute to nothing",
+        py::arg("logits"), py::arg("labels"), py::arg("loss_sum"),
+        py::arg("counts"), py::arg("pred") = c10::nullopt,
+        py::arg("cursor_dev") = c10::nullopt);
   m.def("linear_act_fwd_dev", &linear_act_fwd_dev,
         "linear fwd with device-side dropout offset",
         py::arg("x"), py::arg("w"), py::arg("b"), py::arg("relu"),

@@ -86,6 +86,21 @@ void launch_batch_gather(const uint8_t* img, const uint8_t* lab,
                          const unsigned short* lut, unsigned short* x,
                          long* y, uint32_t N, uint32_t B, uint64_t seed,
                          uint64_t step, const long* step_dev, hipStream_t);
+// eval_ops.hip — device-side evaluation.  range_gather: the sequential chunk
+// [start, start+B) of the resident set (start from the host or *start_dev),
+// rows past N zero-filled with label -1.  softmax_eval: loss / live / correct
+// / confusion counts ACCUMULATED into loss_sum[1] / counts[2 + C*C] over the
+// rows with 0 <= label < C; optional pred[B] (255 = not live) and
+// cursor_dev += B.  part/ticket: its own persistent workspace of
+// SOFTMAX_MAX_BLOCKS floats + one zero-initialised, self-resetting counter.
+void launch_range_gather(const uint8_t* img, const uint8_t* lab,
+                         const unsigned short* lut, unsigned short* x,
+                         long* y, uint32_t N, uint32_t B, uint64_t start,
+                         const long* start_dev, hipStream_t);
+void launch_softmax_eval(const unsigned short* logits, const long* labels,
+                         float* loss_sum, int* counts, uint8_t* pred,
+                         long* cursor_dev, int B, int C, float* part,
+                         unsigned* ticket, hipStream_t);
 void launch_transpose_bf16(const unsigned short* src, unsigned short* dst,
                            int R, int C, hipStream_t);
 struct TransposeDesc {

@@ -22,8 +22,9 @@ import numpy as np
 import torch
 
 from ..ops import functional as Fx
-from .mnist_data import (IMAGE_SIZE, NUM_CHANNELS, PIXEL_DEPTH, TRAIN_IMAGES,
-                         TRAIN_LABELS, extract_images_u8, extract_labels)
+from .mnist_data import (IMAGE_SIZE, NUM_CHANNELS, PIXEL_DEPTH, TEST_IMAGES,
+                         TEST_LABELS, TRAIN_IMAGES, TRAIN_LABELS,
+                         extract_images_u8, extract_labels)
 
 
 def normalisation_lut(dtype: torch.dtype = torch.float32) -> torch.Tensor:
@@ -92,6 +93,31 @@ class DeviceDataSet:
         return Fx.batch_gather(self._images, self._labels, self._lut, x, y,
                                self.seed, step=step, step_dev=step_dev)
 
+    def range_into(self, x: torch.Tensor, y: torch.Tensor, start=None,
+                   start_dev=None):
+        """Write the sequential chunk [start, start + B) into x [B,28,28,1]
+        / y [B]; `start` is a host int or `*start_dev` (device int64;
+        capturable into a hipGraph).  Rows past the end of the set are
+        zero-filled with label -1: evaluation reads the whole set, tail
+        included, in fixed-shape chunks."""
+        if x.dtype != self.dtype:
+            raise TypeError(f"x is {x.dtype}, data set built for {self.dtype}")
+        return Fx.range_gather(self._images, self._labels, self._lut, x, y,
+                               start=start, start_dev=start_dev)
+
+    @classmethod
+    def random(cls, n: int, seed: int, device="cpu",
+               dtype: torch.dtype = torch.float32, worker_id: int = 0,
+               n_workers: int = 1):
+        """Seeded uint8 stand-in (uniform pixels, labels in [0, 10)) for
+        runs without idx-gz files."""
+        rng = np.random.RandomState(seed)
+        img = rng.randint(0, 256, size=(n, IMAGE_SIZE * IMAGE_SIZE),
+                          dtype=np.uint8)
+        lab = rng.randint(0, 10, size=n, dtype=np.uint8)
+        return cls(img, lab, worker_id=worker_id, n_workers=n_workers,
+                   seed=seed, device=device, dtype=dtype)
+
     def batch_at(self, step: int, batch_size: int):
         """(x, y) of the batch at `step` — a pure function of its arguments
         (and the seed)."""
@@ -115,11 +141,17 @@ class DeviceDataSet:
 
 def load_device_mnist(data_dir: str, subset: int = 0, worker_id: int = 0,
                       n_workers: int = 1, shard: bool = True, seed: int = 0,
-                      device="cpu", dtype: torch.dtype = torch.float32):
+                      device="cpu", dtype: torch.dtype = torch.float32,
+                      split: str = "train"):
     """idx-gz train files -> DeviceDataSet holding exactly the examples the
     host-fed path (engine/train.py::make_dataset) trains on: the rank::world
-    shard unless shard=False, then `subset` keeps its first N examples."""
-    paths = [os.path.join(data_dir, f) for f in (TRAIN_IMAGES, TRAIN_LABELS)]
+    shard unless shard=False, then `subset` keeps its first N examples.
+    split="test" reads the t10k pair instead, same shard/subset rules."""
+    if split not in ("train", "test"):
+        raise ValueError(f"split must be 'train' or 'test', not {split!r}")
+    names = ((TRAIN_IMAGES, TRAIN_LABELS) if split == "train"
+             else (TEST_IMAGES, TEST_LABELS))
+    paths = [os.path.join(data_dir, f) for f in names]
     missing = [p for p in paths if not os.path.exists(p)]
     if missing:
         raise FileNotFoundError(

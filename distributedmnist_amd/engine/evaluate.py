@@ -40,11 +40,78 @@ def do_eval(model, images, labels, device, dtype, batch_size: int = 10000):
     return correct_sum / total, loss_sum / total
 
 
-def evaluate(dataset, flags, writer=None):
-    """Poll loop. Returns list of (step, precision, loss)."""
+def resolve_eval_device(flags):
+    """(device, compute dtype) of the evaluator process."""
     device = torch.device(flags.device) if flags.device not in ("auto", "") else (
         torch.device("cuda:0") if torch.cuda.is_available() else torch.device("cpu"))
     dtype = torch.bfloat16 if device.type == "cuda" else torch.float32
+    return device, dtype
+
+
+def evaluate_resident(dataset, flags, writer=None):
+    """--device_data poll loop: `dataset` is a DeviceDataSet already on the
+    evaluator's device (uploaded once, before the loop); the model, its
+    FlatParams and the DeviceEvaluator are built once and every new
+    checkpoint is loaded in place.  Same result lines as evaluate()."""
+    import os
+
+    import numpy as np
+
+    from ..parallel import FlatParams
+    from .device_eval import DeviceEvaluator
+    device, dtype = resolve_eval_device(flags)
+    start_time = time.time()
+    last_step = -1
+    results = []
+    n_evals = 0
+    fp = ev = model_name = None
+    while True:
+        restored = Supervisor.restore(flags.checkpoint_dir)
+        if restored is not None:
+            step, payload = restored
+            if step != last_step:
+                name = payload.get("model", flags.model)
+                if ev is None or name != model_name:
+                    model = build_model(name, seed=payload.get("seed", 66478),
+                                        compute_dtype=dtype).to(device)
+                    fp = FlatParams(model, device=device, compute_dtype=dtype)
+                    ev = DeviceEvaluator(model, dataset,
+                                         flags.eval_batch_size, device)
+                    model_name = name
+                fp.load_flat(payload["flat_master"])
+                print('Succesfully loaded model from %s at step=%s.' %
+                      (Supervisor.latest_checkpoint(flags.checkpoint_dir)[1], step),
+                      flush=True)
+                res = ev.run()
+                print('Num examples: %d  Precision @ 1: %f Loss: %f Time: %f' %
+                      (res.num_examples, res.precision, res.loss,
+                       time.time() - start_time), flush=True)
+                if writer is not None:
+                    writer.add_scalar("Validation Accuracy", res.precision, step)
+                    writer.add_scalar("Validation Loss", res.loss, step)
+                if getattr(flags, "confusion", False):
+                    conf = res.confusion.numpy()
+                    os.makedirs(flags.eval_dir, exist_ok=True)
+                    np.save(os.path.join(flags.eval_dir,
+                                         f"confusion-{step}.npy"), conf)
+                    recall = conf.diagonal() / np.maximum(conf.sum(axis=1), 1)
+                    log.info("step %d per-class recall: %s", step,
+                             " ".join("%d:%.4f" % (c, r)
+                                      for c, r in enumerate(recall)))
+                results.append((step, res.precision, res.loss))
+                last_step = step
+                n_evals += 1
+        if flags.run_once or (flags.max_evals and n_evals >= flags.max_evals):
+            break
+        time.sleep(flags.eval_interval_secs)
+    return results
+
+
+def evaluate(dataset, flags, writer=None):
+    """Poll loop. Returns list of (step, precision, loss)."""
+    if getattr(flags, "device_data", False):
+        return evaluate_resident(dataset, flags, writer=writer)
+    device, dtype = resolve_eval_device(flags)
     start_time = time.time()
     last_step = -1
     results = []

@@ -99,6 +99,18 @@ class Trainer:
         elif 0 < flags.num_replicas_to_aggregate < world:
             mode = "k_of_n"
         self.mode = mode
+        self.eval_every = int(getattr(flags, "eval_every_steps", 0) or 0)
+        if self.eval_every > 0 and mode == "interval":
+            # free-running ranks are not in lockstep: the sharded
+            # evaluation's all_reduce would deadlock
+            raise ValueError(
+                "--eval_every_steps cannot be combined with "
+                "--interval_method; use the polling evaluator "
+                "(src/mnist_eval.py) there")
+        # in-training evaluation (--eval_every_steps > 0): built by train()
+        self.evaluator = None
+        self.test_acc = 0.0      # most recent held-out precision
+        self.eval_history = []   # (step, precision, loss) per evaluation
         self.engine = SyncEngine(
             self.fp.flat_grad, mode=mode,
             replicas_to_aggregate=flags.num_replicas_to_aggregate,
@@ -377,11 +389,37 @@ class Trainer:
         self.fp.refresh_transposes()
         self.num_contributors = contributors
 
+    # -- in-training evaluation (--eval_every_steps) ----------------------
+    def attach_eval_dataset(self, ds):
+        """Build the DeviceEvaluator on `ds`, this rank's DeviceDataSet
+        shard of the held-out set (make_eval_dataset)."""
+        from .device_eval import DeviceEvaluator
+        sharded = self.world > 1 and dist.is_initialized()
+        self.evaluator = DeviceEvaluator(
+            self.model, ds, self.flags.eval_batch_size, self.device,
+            rank=self.rank, world=self.world if sharded else 1)
+        return self.evaluator
+
+    def evaluate_now(self, writer=None):
+        """One held-out evaluation of the current weights; the precision
+        rides on the following step lines."""
+        res = self.evaluator.run()
+        self.test_acc = res.precision
+        self.eval_history.append((self.step, res.precision, res.loss))
+        if writer is not None:
+            writer.add_scalar("Validation Accuracy", res.precision, self.step)
+            writer.add_scalar("Validation Loss", res.loss, self.step)
+        return res
+
     # ------------------------------------------------------------------
     def train(self, dataset, max_steps=None):
         flags = self.flags
         self._num_examples = dataset.num_examples
         max_steps = max_steps if max_steps is not None else flags.max_steps
+        if self.eval_every > 0 and self.evaluator is None:
+            self.attach_eval_dataset(make_eval_dataset(
+                flags, self.rank, self.world, self.device,
+                self.compute_dtype))
         sv = Supervisor(flags.train_dir, flags.save_interval_secs,
                         is_chief=self.is_chief)
         restored = Supervisor.restore(flags.train_dir) if os.path.isdir(flags.train_dir) else None
@@ -443,12 +481,17 @@ class Trainer:
             loss_v, acc_v = float(loss_v), float(acc_v)
             duration = finish_time - start_time
             examples_per_sec = flags.batch_size / duration
+            if self.eval_every > 0 and (self.step % self.eval_every == 0
+                                        or self.step >= max_steps):
+                # after the update that made self.step a multiple of N, and
+                # once more after the last step; outside the step's timing
+                self.evaluate_now(writer)
             # per-step line: scraper contract (benchmark.py:31 'step (\d+),')
             log.info("Worker %d: %s: step %d, loss = %f, train_acc = %f, "
                      "test_acc = %f(%.1f examples/sec; %.3f  sec/batch)",
                      self.rank, datetime.datetime.now(), self.step, loss_v,
-                     acc_v, 0.0, examples_per_sec, duration)
-            time_acc_list.append((finish_time, acc_v, 0.0, loss_v))
+                     acc_v, self.test_acc, examples_per_sec, duration)
+            time_acc_list.append((finish_time, acc_v, self.test_acc, loss_v))
             if self.step % flags.save_results_period == 0:
                 path = os.path.join(flags.train_dir,
                                     f"worker{self.rank}_time_acc.npy")
@@ -521,6 +564,19 @@ def make_dataset(flags, rank: int, world: int, device, dtype):
                         train.labels[:flags.subset], shard=False,
                         seed=flags.seed + rank)
     return train
+
+
+def make_eval_dataset(flags, rank: int, world: int, device, dtype):
+    """This rank's resident shard of the held-out set for
+    --eval_every_steps: the t10k idx-gz pair, or the seeded uint8 stand-in
+    (the evaluator CLI's synthetic seed) without files.  Always sharded
+    rank::world — the evaluator sums the shards' statistics."""
+    from ..data import load_device_mnist
+    if flags.synthetic_data or flags.fake_data:
+        return DeviceDataSet.random(10000, 4242, device=device, dtype=dtype,
+                                    worker_id=rank, n_workers=world)
+    return load_device_mnist(flags.data_dir, worker_id=rank, n_workers=world,
+                             device=device, dtype=dtype, split="test")
 
 
 def train_main(flags):

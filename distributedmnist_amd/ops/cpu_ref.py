@@ -264,3 +264,57 @@ def batch_gather(img_u8, lab_u8, lut, x, y, seed: int, step: int):
     x.copy_(lut[img_u8[idx].long()].reshape(x.shape))
     y.copy_(lab_u8[idx].long())
     return x, y
+
+
+# ---------------------------------------------------------------------------
+# Device-side evaluation: sequential chunk gather + accumulated statistics.
+# Oracles of csrc/eval_ops.hip (and the CPU / fp32-on-GPU path).
+# ---------------------------------------------------------------------------
+
+def range_gather(img_u8, lab_u8, lut, x, y, start: int):
+    """Chunk [start, start + B) of the resident set into the caller's
+    buffers: a row i < N is lut[img_u8[i]] with its label, a row past N is
+    exactly zero with label -1.  start >= N is legal (all padding)."""
+    n, b = lab_u8.shape[0], y.shape[0]
+    start = int(start)
+    if start < 0:
+        raise ValueError("start must be >= 0")
+    live = max(0, min(b, n - start))
+    xf = x.view(b, -1)
+    if live:
+        xf[:live] = lut[img_u8[start:start + live].long()]
+        y[:live] = lab_u8[start:start + live].long()
+    if live < b:
+        xf[live:] = 0
+        y[live:] = -1
+    return x, y
+
+
+def softmax_eval(logits, labels, loss_sum, counts, pred=None,
+                 cursor_dev=None):
+    """Evaluation statistics of one chunk, ACCUMULATED into the running
+    state: loss_sum[0] (fp32) += sum of -log softmax(logits)[label],
+    counts (int32 [2 + C*C]) += (live rows, correct rows, confusion[t, p]).
+    A row is live iff 0 <= label < C; every other row contributes to
+    nothing.  The prediction is the LOWEST index among the maximal logits
+    (not torch.argmax, whose tie order is unspecified).  pred (uint8 [B]):
+    predicted class, 255 where the row is not live.  cursor_dev (int64 [1])
+    advances by B."""
+    B, C = logits.shape
+    lf = logits.float()
+    live = (labels >= 0) & (labels < C)
+    mx = lf.max(dim=1, keepdim=True).values
+    idx = torch.arange(C, device=logits.device).expand(B, C)
+    p = torch.where(lf == mx, idx, torch.full_like(idx, C)).min(dim=1).values
+    t = labels.clamp(0, C - 1)
+    xl = lf.gather(1, t.view(-1, 1)).squeeze(1)
+    row_loss = (lf - mx).exp().sum(dim=1).log() - (xl - mx.squeeze(1))
+    loss_sum += row_loss[live].double().sum().to(loss_sum.dtype)
+    tl, pl = t[live], p[live]
+    counts[0] += int(live.sum())
+    counts[1] += int((tl == pl).sum())
+    counts[2:] += torch.bincount(tl * C + pl, minlength=C * C).to(counts.dtype)
+    if pred is not None:
+        pred.copy_(torch.where(live, p, torch.full_like(p, 255)).to(pred.dtype))
+    if cursor_dev is not None:
+        cursor_dev += B

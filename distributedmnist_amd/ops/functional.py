@@ -220,6 +220,44 @@ def batch_gather(img_u8: torch.Tensor, lab_u8: torch.Tensor,
     return x, y
 
 
+def range_gather(img_u8: torch.Tensor, lab_u8: torch.Tensor,
+                 lut: torch.Tensor, x: torch.Tensor, y: torch.Tensor,
+                 start: int | None = None, start_dev=None):
+    """Sequential chunk [start, start + B) of the resident uint8 set into
+    the caller's buffers, tail included: rows past N are zero-filled with
+    label -1 (ops/cpu_ref.py::range_gather).  Exactly one of `start` (host
+    int) / `start_dev` (device int64, hipGraph-capturable on the HIP path)
+    is given.  Unlike batch_gather, B > N and start >= N are legal."""
+    if (start is None) == (start_dev is None):
+        raise ValueError("range_gather: pass exactly one of start / start_dev")
+    if _use_hip(x):
+        _C.ext().range_gather(img_u8, lab_u8, lut, x, y,
+                              0 if start is None else int(start),
+                              start_dev=start_dev)
+    else:
+        if start is None:
+            start = int(start_dev.item())  # reference path: host sync is fine
+        cpu_ref.range_gather(img_u8, lab_u8, lut, x, y, int(start))
+    return x, y
+
+
+def softmax_eval(logits: torch.Tensor, labels: torch.Tensor,
+                 loss_sum: torch.Tensor, counts: torch.Tensor, pred=None,
+                 cursor_dev=None):
+    """Accumulate one chunk's evaluation statistics into the running state
+    (loss_sum fp32 [1], counts int32 [2 + C*C]: live rows, correct rows,
+    confusion[true, predicted]); rows whose label lies outside [0, C)
+    contribute to nothing.  Optional pred (uint8 [B], 255 = not live) and
+    cursor_dev (int64 [1], advanced by B).  No autograd: this is the
+    evaluation kernel, it produces no dlogits."""
+    if _use_hip(logits):
+        _C.ext().softmax_eval(logits, labels, loss_sum, counts, pred=pred,
+                              cursor_dev=cursor_dev)
+    else:
+        cpu_ref.softmax_eval(logits, labels, loss_sum, counts, pred=pred,
+                             cursor_dev=cursor_dev)
+
+
 def sgd_step(master: torch.Tensor, grad: torch.Tensor, lr: float,
              grad_scale: float = 1.0, drop_connect_keep=None,
              seed: int = 0, offset: int = 0, shadow=None,

@@ -92,6 +92,14 @@ def build_train_parser() -> argparse.ArgumentParser:
                         "when the step is captured); the batch order is a "
                         "pure function of (seed, rank, step). No effect "
                         "with --synthetic_data / --fake_data")
+    p.add_argument("--eval_every_steps", type=int, default=0,
+                   help=">0: keep the test set on the device and evaluate it "
+                        "every N steps (and after the last step); the step "
+                        "line's test_acc and column 2 of the time/accuracy "
+                        "npy carry the most recent precision. Not with "
+                        "--interval_method")
+    p.add_argument("--eval_batch_size", type=int, default=1000,
+                   help="chunk size of the in-training evaluation")
     return p
 
 
@@ -108,6 +116,16 @@ def build_eval_parser() -> argparse.ArgumentParser:
     p.add_argument("--model", default="lenet", choices=["lenet", "mlp"])
     p.add_argument("--device", default="auto")
     p.add_argument("--max_evals", type=int, default=0, help="0 = run forever")
+    p.add_argument("--device_data", action="store_true",
+                   help="keep the test set on the device as uint8 and "
+                        "evaluate every checkpoint there (model and buffers "
+                        "built once, checkpoints loaded in place)")
+    p.add_argument("--eval_batch_size", type=int, default=1000,
+                   help="chunk size of the --device_data evaluation")
+    p.add_argument("--confusion", action="store_true",
+                   help="with --device_data: also save "
+                        "eval_dir/confusion-<step>.npy and log per-class "
+                        "recall")
     return p
 
 

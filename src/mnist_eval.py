@@ -20,7 +20,21 @@ def main(argv=None):
     if os.path.exists(flags.eval_dir):
         shutil.rmtree(flags.eval_dir, ignore_errors=True)
     os.makedirs(flags.eval_dir, exist_ok=True)
-    if flags.synthetic_data:
+    if flags.device_data:
+        # the test set goes to the device once, as uint8, before the poll
+        # loop; without files it is the seeded uint8 stand-in
+        from distributedmnist_amd.data import (DeviceDataSet,
+                                               load_device_mnist)
+        from distributedmnist_amd.engine.evaluate import resolve_eval_device
+        device, dtype = resolve_eval_device(flags)
+        if flags.synthetic_data or flags.fake_data:
+            dataset = DeviceDataSet.random(10000, 4242, device=device,
+                                           dtype=dtype)
+        else:
+            dataset = load_device_mnist(flags.data_dir, shard=False,
+                                        device=device, dtype=dtype,
+                                        split="test")
+    elif flags.synthetic_data:
         import torch
 
         class _SynthEval:
