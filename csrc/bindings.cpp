@@ -35,6 +35,15 @@ int pick_splitk(int mtiles, int ntiles, int ksteps) {
   return want;
 }
 
+// Largest split <= want that leaves no k-slice empty: the kernels give each
+// slice ceil(ksteps/splitk) steps of THEIR K-step, so the last slice starts
+// at (splitk-1)*ceil(ksteps/splitk), which must be < ksteps.
+int clamp_splitk(int want, int ksteps) {
+  int s = std::max(1, std::min(want, ksteps));
+  int per = cdiv(ksteps, s);
+  return cdiv(ksteps, per);
+}
+
 // glds + tr16 dW staging (dw_tr.hip); DMNIST_DW_TR=0 reverts to the
 // scatter-staged gemm_tile path for A/B comparison
 int dw_tr_level() {
@@ -52,6 +61,60 @@ bool dw_tr_enabled() { return dw_tr_level() != 0; }
 bool conv2_dw_slab_route(int H, int W, int Cin, int Cout) {
   return conv2_dw_slab_supported(H, W, Cin, Cout) && dw_tr_enabled() &&
          conv2_dw_slab_enabled() && !getenv("DMNIST_DW_SPREAD");
+}
+
+// fc dW (dW += x^T dyeff) route: tile shape and split of the batch axis.
+// tr = 1: dw_tr_kernel<bn, AM_PLAIN, tbm>; tr = 0: the scatter-staged
+// gemm_tile path (tbm = bn = its square tile).  Both kernels step the batch
+// axis by 64, so the split is clamped against cdiv(B, 64) and never leaves a
+// slice empty.  splitk == 1 on the tr route is single-writer (no atomics)
+// when the bucket view is 16 B aligned.
+// DMNIST_DW_PLAN (read per call): "0" keeps the pre-plan choice (128-row
+// tiles, split from pick_splitk); "tbm,bn,splitk" forces one (sweeps).
+struct DwPlan { int tr, tbm, bn, splitk; };
+DwPlan linear_dw_plan(int K, int N, int B) {
+  const int ksteps = cdiv(B, 64);
+  if (!(dw_tr_enabled() && K % 8 == 0 && N % 64 == 0)) {
+    int bm = cdiv(K, 128) * cdiv(N, 128) >= 128 ? 128 : 64;
+    int want = pick_splitk(cdiv(K, bm), cdiv(N, bm), cdiv(B, 32));
+    return {0, bm, bm, clamp_splitk(want, ksteps)};
+  }
+  int bn = (N % 128 == 0) ? 128 : 64;
+  DwPlan old{1, 128, bn,
+             clamp_splitk(pick_splitk(cdiv(K, 128), cdiv(N, bn), cdiv(B, 32)),
+                          ksteps)};
+  if (const char* e = getenv("DMNIST_DW_PLAN")) {
+    int tbm = 0, fbn = 0, sk = 0;
+    if (sscanf(e, "%d,%d,%d", &tbm, &fbn, &sk) == 3 &&
+        (tbm == 64 || tbm == 128) && (fbn == 64 || fbn == 128) &&
+        N % fbn == 0)
+      return {1, tbm, fbn, clamp_splitk(sk, ksteps)};
+    return old;
+  }
+  // Problems whose 64-row tiles fill the chip by themselves (fc1: 49 x 8 =
+  // 392 blocks of 64 x 64) need no deep split to find parallelism, and the
+  // flush (one fp32 atomic per element per slice) is what the short batches
+  // pay for.  Measured on fc1, solo (profiles/fc1_epilogues_b1024_b8192.md):
+  // B=1024 single-writer 64x64 17.6 us against 27.7; B=2048 / 4096 64x128
+  // split 2 25.8 / 36.6 against 33.7 / 43.0; at B=8192 the pre-plan choice
+  // (57.8) is level with the best of the sweep (57.4) and stays.  The tier
+  // edges sit halfway between the measured batches.
+  if (cdiv(K, 64) * cdiv(N, 64) >= 256) {
+    if (B < 1536) return {1, 64, 64, 1};
+    if (B < 6144) return {1, 64, bn, clamp_splitk(2, ksteps)};
+  }
+  return old;
+}
+
+void launch_linear_dw(GemmParams& p, int K, int N, int B, hipStream_t s) {
+  DwPlan pl = linear_dw_plan(K, N, B);
+  p.splitk = pl.splitk;
+  if (pl.tr) {
+    bool sw = pl.splitk == 1 && ((uintptr_t)p.C & 15) == 0 && p.ldc % 4 == 0;
+    gemm_dw_tr(p, pl.tbm, pl.bn, sw, s);
+  } else {
+    (pl.tbm == 128 ? gemm_dw_128 : gemm_dw_64)(p, s);
+  }
 }
 
 // --------------------------------------------------------------------------
@@ -100,18 +163,47 @@ torch::Tensor linear_act_fwd_impl(torch::Tensor x, torch::Tensor w,
                             x.options().dtype(at::kFloat));
     p.C = acc.data_ptr();
     p.splitk = sk;
+    // In-kernel fix-up, DMNIST_FC_FIXUP=1 (read per call): the last slice
+    // block of a tile sums the planes and writes y, no second launch.  NOT
+    // dispatched by default: publishing the fp32 planes across the XCDs
+    // costs more than the launch it saves (fc1 @B=1024 solo: 35 us against
+    // 28 us for the two launches; step 0.277-0.279 against 0.269-0.270 ms,
+    // docs/KERNELS.md).  One zeroed, self-resetting ticket per tile (tiles64
+    // < 256 on this route) lives in a per-device workspace, allocated on
+    // the first call outside graph capture.  Like softmax's workspace it
+    // serves ONE launch at a time per device: split-K forwards of one
+    // device must be ordered on a stream (or graph), never concurrent.
+    const char* fe = getenv("DMNIST_FC_FIXUP");
+    bool fixup = fe && atoi(fe) != 0 && N % 8 == 0;
+    if (fixup) {
+      static std::vector<torch::Tensor>* ws = new std::vector<torch::Tensor>(64);
+      int dev = x.get_device();
+      TORCH_CHECK(dev >= 0 && dev < 64, "linear_act_fwd: bad device index");
+      if (!(*ws)[dev].defined()) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        hipStreamIsCapturing(s, &cap);
+        TORCH_CHECK(cap == hipStreamCaptureStatusNone,
+                    "linear_act_fwd: first split-K call on a device allocates "
+                    "its ticket workspace and must run outside graph capture");
+        (*ws)[dev] = torch::zeros({256}, x.options().dtype(at::kInt));
+      }
+      p.tickets = reinterpret_cast<unsigned*>((*ws)[dev].data_ptr<int>());
+      p.Y = bf16_mut(y);
+      p.relu = relu ? 1 : 0;
+    }
     if (bt) {
       CHECK_BF16((*wT)); CHECK_CONTIG((*wT));
       TORCH_CHECK(wT->size(0) == N && wT->size(1) == K, "wT shape mismatch");
       p.B = bf16_ptr(*wT); p.ldb = K;
-      gemm_fwd_slices_64_bt(p, s);
+      (fixup ? gemm_fwd_slices_fix_64_bt : gemm_fwd_slices_64_bt)(p, s);
     } else {
       p.B = bf16_ptr(w); p.ldb = N;
-      gemm_fwd_slices_64(p, s);
+      (fixup ? gemm_fwd_slices_fix_64 : gemm_fwd_slices_64)(p, s);
     }
-    launch_fwd_epilogue(acc.data_ptr<float>(), b.data_ptr<float>(),
-                        bf16_mut(y), M, N, sk, relu ? 1 : 0, (float)p_keep,
-                        (uint64_t)seed, (uint64_t)offset, offset_dev, s);
+    if (!fixup)
+      launch_fwd_epilogue(acc.data_ptr<float>(), b.data_ptr<float>(),
+                          bf16_mut(y), M, N, sk, relu ? 1 : 0, (float)p_keep,
+                          (uint64_t)seed, (uint64_t)offset, offset_dev, s);
     return y;
   }
   if (bt) {
@@ -187,16 +279,7 @@ std::vector<torch::Tensor> linear_act_bwd_impl(torch::Tensor dy, torch::Tensor x
     p.M = K; p.N = N; p.K = B;
     p.lda = K;  // A_T: A[m][k'] = x[k'*lda + m]
     p.ldb = N; p.ldc = N;
-    if (dw_tr_enabled() && K % 8 == 0 && N % 64 == 0) {
-      int bn = (N % 128 == 0) ? 128 : 64;
-      p.splitk = pick_splitk(cdiv(K, 128), cdiv(N, bn), cdiv(B, 32));
-      (bn == 128 ? gemm_dw_tr_128 : gemm_dw_tr_64)(p, s);
-    } else {
-      bool big = cdiv(K, 128) * cdiv(N, 128) >= 128;
-      int bm = big ? 128 : 64;
-      p.splitk = pick_splitk(cdiv(K, bm), cdiv(N, bm), cdiv(B, 32));
-      (big ? gemm_dw_128 : gemm_dw_64)(p, s);
-    }
+    launch_linear_dw(p, K, N, B, s);
   }
   torch::Tensor dx;
   if (need_dx) {
@@ -421,16 +504,7 @@ void linear_dw_into(torch::Tensor x, torch::Tensor dyeff,
   p.C = dw_out.data_ptr();
   p.M = K; p.N = N; p.K = B;
   p.lda = K; p.ldb = N; p.ldc = N;
-  if (dw_tr_enabled() && K % 8 == 0 && N % 64 == 0) {
-    int bn = (N % 128 == 0) ? 128 : 64;
-    p.splitk = pick_splitk(cdiv(K, 128), cdiv(N, bn), cdiv(B, 32));
-    (bn == 128 ? gemm_dw_tr_128 : gemm_dw_tr_64)(p, cur_stream());
-    return;
-  }
-  bool big = cdiv(K, 128) * cdiv(N, 128) >= 128;
-  int bm = big ? 128 : 64;
-  p.splitk = pick_splitk(cdiv(K, bm), cdiv(N, bm), cdiv(B, 32));
-  (big ? gemm_dw_128 : gemm_dw_64)(p, cur_stream());
+  launch_linear_dw(p, K, N, B, cur_stream());
 }
 
 torch::Tensor linear_dx(torch::Tensor dyeff, torch::Tensor w) {
@@ -471,9 +545,20 @@ torch::Tensor linear_dx_unpool(torch::Tensor dyeff, torch::Tensor w,
   p.CHo = Ho; p.CWo = Wo; p.Cout = C;
   p.amax = amax.data_ptr<uint8_t>();
   p.db = db_out.defined() ? db_out.data_ptr<float>() : nullptr;
+  // C % 64 == 0: every 64-column chunk of a tile is 64 channels of one
+  // pooled pixel, so the epilogue stages the tile in LDS and stores whole
+  // 128 B lines of dact.  DMNIST_UNPOOL_LINES=0 (read per call) keeps the
+  // per-element 2-byte stores; other channel counts always take them.
+  const char* le = getenv("DMNIST_UNPOOL_LINES");
+  p.unpool_lines = !(le && atoi(le) == 0) && C % 64 == 0 &&
+                   ((uintptr_t)p.amax & 15) == 0 && ((uintptr_t)p.C & 15) == 0;
   // 128-tile under ~2 blocks/CU is grid-starved (PMC: 57% parked at
-  // B=1024's 200-block grid); 64-tiles quadruple the grid
-  bool big = cdiv(B, 128) * cdiv(K, 128) >= 512;
+  // B=1024's 200-block grid); 64-tiles quadruple the grid.  With line
+  // stores the 128-tile already wins at 400 blocks (fc1 @B=2048: 49.7 us
+  // against 59.5; at B=1024 it loses 40.8 to 36.6).
+  bool big = cdiv(B, 128) * cdiv(K, 128) >= (p.unpool_lines ? 400 : 512);
+  // DMNIST_UNPOOL_TILE=64|128 forces either tile at any B (read per call)
+  if (const char* e = getenv("DMNIST_UNPOOL_TILE")) big = atoi(e) >= 128;
   (big ? gemm_dx_unpool_128 : gemm_dx_unpool_64)(p, cur_stream());
   return dact;
 }
@@ -934,6 +1019,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "dx GEMM fused with maxpool2x2 backward scatter + conv db",
         py::arg("dyeff"), py::arg("w"), py::arg("amax"),
         py::arg("db_out"), py::arg("Ho"), py::arg("Wo"), py::arg("C"));
+  m.def("linear_dw_plan", [](int64_t K, int64_t N, int64_t B) {
+    DwPlan pl = linear_dw_plan((int)K, (int)N, (int)B);
+    return std::make_tuple(pl.tbm, pl.bn, pl.splitk);
+  }, "(tbm, bn, splitk) the fc dW launcher picks for x[B,K], dyeff[B,N]");
   m.def("pool_scatter", &pool_scatter, "maxpool bwd scatter + conv db");
   m.def("conv_dw_into", &conv_dw_into, "conv dW into bucket view");
   m.def("conv1_dw_pooled", &conv1_dw_pooled,

@@ -24,7 +24,11 @@
 // Modes: AM_PLAIN  A[m][k] = Asrc[k*lda + m]                (fc dW: x^T)
 //        AM_CONV5  A[m=(khkw,ci)][k=pixel] 5x5-SAME gather  (conv dW)
 // Requirements: M % 8 == 0, N % BN == 0, Cin % 8 == 0 (conv), 16B-aligned
-// sources.  Output: fp32 split-K atomics straight into the grad bucket.
+// sources.  Output: fp32 split-K atomics straight into the grad bucket, or
+// (SW = 1, splitk == 1) a single-writer read-add-write: the MFMA operands
+// are swapped so a lane holds four consecutive n of one m and flushes them
+// as one 16 B read-add-write — every gradient element is touched once, by
+// one lane, so the result is bitwise reproducible.
 
 #include "common.h"
 #include "kernels.h"
@@ -35,7 +39,8 @@ __device__ __align__(16) unsigned short g_zero_page[8];  // zero-init
 
 enum { AM_PLAIN = 0, AM_CONV5 = 1 };
 
-template <int BN, int AMODE, int TBM = 128, int TBK = 64, int NBUF = 2>
+template <int BN, int AMODE, int TBM = 128, int TBK = 64, int NBUF = 2,
+          int SW = 0>
 __global__ __launch_bounds__(NT) void dw_tr_kernel(GemmParams p) {
   static_assert(TBK % 32 == 0, "TBK in 32-k MFMA halves");
   static_assert(NBUF == 2 || NBUF == 3, "2-buf overlap or 3-buf glds span");
@@ -93,14 +98,16 @@ __global__ __launch_bounds__(NT) void dw_tr_kernel(GemmParams p) {
   // fetches LOGICAL chunk pc ^ xs(rt), with xs(rt) = (rt ^ (rt>>4)) & 15
   // for A (16 chunks/row) and (rt ^ (rt>>3)) & 7 for B.  rt depends only
   // on (wave, q, lane) — never on the K-tile — so decodes stay loop-
-  // invariant.  The tr16 addresses apply the same xs per slot row.
+  // invariant.  The tr16 addresses apply the same xs per slot row.  An
+  // 8-chunk A row (TBM = 64) takes B's 8-chunk form.
+  constexpr int ASH = (ALPR == 16) ? 4 : 3;
   int amc[AQ];     // logical m column this lane stages, per glds instr
   bool am_ok[AQ];
   int akh[AQ], akw[AQ], aci[AQ];
 #pragma unroll
   for (int q = 0; q < AQ; ++q) {
     int rt = (wave * AQ + q) * (512 / TBM) + lane / ALPR;
-    int xs = (rt ^ (rt >> 4)) & (ALPR - 1);
+    int xs = (rt ^ (rt >> ASH)) & (ALPR - 1);
     amc[q] = m0 + ((lane % ALPR) ^ xs) * 8;
     am_ok[q] = amc[q] < p.M;
     if (AMODE == AM_CONV5) {
@@ -195,7 +202,7 @@ __global__ __launch_bounds__(NT) void dw_tr_kernel(GemmParams p) {
       short8 af[MI], bf[NI];
       // slot address with the matching XOR chunk swizzle (see staging note)
       const auto aswz = [&](int r, int cb) {
-        int xs = (r ^ (r >> 4)) & (ALPR - 1);
+        int xs = (r ^ (r >> ASH)) & (ALPR - 1);
         return abase + (unsigned)(r * (TBM * 2) + (((cb >> 4) ^ xs) << 4) +
                                   (cb & 15));
       };
@@ -225,8 +232,10 @@ __global__ __launch_bounds__(NT) void dw_tr_kernel(GemmParams p) {
       for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              af[mi], bf[ni], acc[mi][ni], 0, 0, 0);
+          acc[mi][ni] = SW ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                                 bf[ni], af[mi], acc[mi][ni], 0, 0, 0)
+                           : __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                                 af[mi], bf[ni], acc[mi][ni], 0, 0, 0);
     }
   };
 
@@ -275,6 +284,22 @@ __global__ __launch_bounds__(NT) void dw_tr_kernel(GemmParams p) {
   // atomics over 16 separate planes (outputs meaningless; isolates the
   // same-address atomic serialization cost in the flush)
   if (p.offset) outp += (size_t)(bz & 15) * p.M * p.ldc;
+  if (SW) {
+    // acc[mi][ni] = D[n = frow + r][m = fcol]: four consecutive n per lane
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi) {
+      int gr = m0 + wr * WM + mi * 16 + fcol;
+      if (gr >= p.M) continue;
+#pragma unroll
+      for (int ni = 0; ni < NI; ++ni) {
+        int gc = n0 + wc * WN + ni * 16 + frow;
+        if (gc >= p.N) continue;  // N % BN == 0: a quad is all in or all out
+        f32x4* o = reinterpret_cast<f32x4*>(outp + (size_t)gr * p.ldc + gc);
+        *o = *o + acc[mi][ni];
+      }
+    }
+    return;
+  }
 #pragma unroll
   for (int mi = 0; mi < MI; ++mi) {
 #pragma unroll
@@ -325,12 +350,22 @@ void conv_dw_tr(const GemmParams& p, hipStream_t s) {
                        s, p);
 }
 
-void gemm_dw_tr_128(const GemmParams& p, hipStream_t s) {
-  dim3 grid(cdiv_h(p.M, 128) * cdiv_h(p.N, 128) * p.splitk);
-  hipLaunchKernelGGL((dw_tr_kernel<128, AM_PLAIN>), grid, dim3(NT), 0, s, p);
+template <int BN, int TBM>
+static void dw_tr_plain(const GemmParams& p, bool sw, hipStream_t s) {
+  dim3 grid(cdiv_h(p.M, TBM) * cdiv_h(p.N, BN) * p.splitk);
+  if (sw)
+    hipLaunchKernelGGL((dw_tr_kernel<BN, AM_PLAIN, TBM, 64, 2, 1>), grid,
+                       dim3(NT), 0, s, p);
+  else
+    hipLaunchKernelGGL((dw_tr_kernel<BN, AM_PLAIN, TBM>), grid, dim3(NT), 0,
+                       s, p);
 }
 
-void gemm_dw_tr_64(const GemmParams& p, hipStream_t s) {
-  dim3 grid(cdiv_h(p.M, 128) * cdiv_h(p.N, 64) * p.splitk);
-  hipLaunchKernelGGL((dw_tr_kernel<64, AM_PLAIN>), grid, dim3(NT), 0, s, p);
+void gemm_dw_tr(const GemmParams& p, int tbm, int bn, bool single_writer,
+                hipStream_t s) {
+  bool sw = single_writer && p.splitk == 1;
+  if (tbm == 64)
+    (bn == 128 ? dw_tr_plain<128, 64> : dw_tr_plain<64, 64>)(p, sw, s);
+  else
+    (bn == 128 ? dw_tr_plain<128, 128> : dw_tr_plain<64, 128>)(p, sw, s);
 }

@@ -46,7 +46,11 @@ enum Epi { EPI_NONE = 0, EPI_BIAS = 1, EPI_BIAS_RELU = 2, EPI_BIAS_RELU_DROP = 3
 // kernel into the producing dX GEMM (reference backward chain
 // mnist.py:115-127), removing one critical-path kernel + the pooled-grad
 // round trip.
-enum OutKind { OUT_BF16 = 0, OUT_F32_ATOMIC = 1, OUT_F32_SLICES = 2 };
+// OUT_F32_SLICES_FIX: OUT_F32_SLICES whose last block per tile also sums the
+// planes and writes the bf16 result (its own instantiation, so the plain
+// slices kernel carries none of it)
+enum OutKind { OUT_BF16 = 0, OUT_F32_ATOMIC = 1, OUT_F32_SLICES = 2,
+               OUT_F32_SLICES_FIX = 3 };
 
 #define NTHREADS 256
 #define BK 64
@@ -266,14 +270,42 @@ void gemm_tile_kernel(GemmParams p) {
   constexpr int CHB = (BN * BK / 8) / NTHREADS;
   constexpr int DB = (PIPE == 1) ? 2 : 1;
   static_assert(CHA >= 1 && CHB >= 1, "tile too small for 256 threads");
-  __shared__ __align__(16) ushort_t As[DB][BM][LDK];
-  __shared__ __align__(16) ushort_t Bs[DB][BN][LDK];
+  // one raw buffer: the operand images during the k-loop; the EPI_UNPOOL
+  // line-store epilogue reuses it for the amax tile and the output staging
+  constexpr int A_BYTES = DB * BM * LDK * 2, B_BYTES = DB * BN * LDK * 2;
+  __shared__ __align__(16) unsigned char smem[A_BYTES + B_BYTES];
+  ushort_t (*As)[BM][LDK] = reinterpret_cast<ushort_t (*)[BM][LDK]>(smem);
+  ushort_t (*Bs)[BN][LDK] =
+      reinterpret_cast<ushort_t (*)[BN][LDK]>(smem + A_BYTES);
   // EPI_UNPOOL / EPI_MASK_DB: per-column bias-grad partials, flushed once
   constexpr bool HAS_DB = (EPI == EPI_UNPOOL || EPI == EPI_MASK_DB);
   __shared__ float dbred[HAS_DB ? BN : 1];
   if (HAS_DB && threadIdx.x < BN) dbred[threadIdx.x] = 0.f;
 
   const int tid = threadIdx.x;
+  // EPI_UNPOOL line-store path (host sets p.unpool_lines when Cout % 64 ==
+  // 0): a 64-column chunk of the tile is 64 channels of ONE pooled pixel,
+  // so each (row, window position) is one contiguous, 128 B-aligned 128 B
+  // line of dact.  The amax tile is fetched here with 16 B loads so it is
+  // in registers when the k-loop ends.
+  constexpr bool UNP = (EPI == EPI_UNPOOL) && (BN % 64 == 0) &&
+                       (BM * BN / 16) % NTHREADS == 0 && SWZ == 0;
+  constexpr int NAM = UNP ? (BM * BN / 16) / NTHREADS : 1;
+  const bool use_lines = UNP && p.unpool_lines;
+  uint4 amreg[NAM];
+  if (use_lines) {
+    const int am_m0 = blockIdx.x * BM, am_n0 = blockIdx.y * BN;
+#pragma unroll
+    for (int i = 0; i < NAM; ++i) {
+      int idx = tid + i * NTHREADS;
+      int gr = am_m0 + idx / (BN / 16);
+      int gc = am_n0 + (idx % (BN / 16)) * 16;
+      amreg[i] = uint4{0x07070707u, 0x07070707u, 0x07070707u, 0x07070707u};
+      if (gr < p.M && gc < p.N)  // N % 64 == 0: a chunk is all in or all out
+        amreg[i] = *reinterpret_cast<const uint4*>(p.amax + (size_t)gr * p.N + gc);
+    }
+  }
+
   const int lane = tid & 63;
   const int wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1;
@@ -423,6 +455,84 @@ epilogue:
   if (EPI == EPI_UNPOOL || EPI == EPI_MASK_DB)
 #pragma unroll
     for (int ni = 0; ni < NI; ++ni) dbloc[ni] = 0.f;
+  if constexpr (UNP) {
+    if (use_lines) {
+      // A pass stages 64 (row, 64-column chunk) slots x 4 window positions
+      // x 128 B = 32 KB: the whole 64-tile, or one mi of the 128-tile.
+      // Slot s, position q, channel c sits at (s*4 + q)*128 + 2*c with the
+      // 16 B chunk index XORed by 2*((row>>2)&3): the four 16-lane groups of
+      // a wave (rows 4 apart, same columns) then write four different 32 B
+      // spans of a line instead of one.  The amax tile [BM][BN] bytes sits
+      // behind the staging, its 16 B chunks XORed by (row>>2)&3 for the
+      // same reason.
+      constexpr int NJ = BN / 64;       // 64-column chunks per tile row
+      constexpr int MPP = 2 / NJ;       // mi per pass
+      constexpr int PR = MPP * 16;      // rows per wave-row per pass
+      constexpr int STG = 64 * 4 * 128;
+      static_assert(MI % MPP == 0, "passes cover whole mi groups");
+      static_assert(STG + BM * BN <= A_BYTES + B_BYTES, "staging fits LDS");
+      unsigned char* ams = smem + STG;
+      ushort_t* dact = reinterpret_cast<ushort_t*>(p.C);
+      const int H2 = p.CHo * 2, W2 = p.CWo * 2;
+      const int key = lane >> 4;        // (row >> 2) & 3 of this lane's rows
+      __syncthreads();  // every wave is done reading the operand images
+#pragma unroll
+      for (int i = 0; i < NAM; ++i) {
+        int idx = tid + i * NTHREADS;
+        int row = idx / (BN / 16), ch = idx % (BN / 16);
+        *reinterpret_cast<uint4*>(ams + row * BN +
+                                  ((ch ^ ((row >> 2) & 3)) << 4)) = amreg[i];
+      }
+#pragma unroll
+      for (int pass = 0; pass < MI / MPP; ++pass) {
+        __syncthreads();  // amax tile written / previous pass's lines read
+#pragma unroll
+        for (int mm = 0; mm < MPP; ++mm) {
+          const int mi = pass * MPP + mm;
+#pragma unroll
+          for (int ni = 0; ni < NI; ++ni) {
+            const int colt = wc * WN + ni * 16 + fcol;
+            const int j = colt >> 6, c = colt & 63;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int rowt = wr * WM + mi * 16 + frow + r;
+              const int lr = wr * PR + mm * 16 + frow + r;
+              // rows >= M and columns >= N were prefetched as 7 (dead)
+              int pos = ams[rowt * BN + (((colt >> 4) ^ key) << 4) + (colt & 15)];
+              float g = pos < 4 ? acc[mi][ni][r] : 0.f;
+              dbloc[ni] += g;
+              ushort_t gb = f2bf(g);
+              unsigned char* sp = smem + ((lr * NJ + j) * 4) * 128 +
+                                  (((c >> 3) ^ (key << 1)) << 4) + (c & 7) * 2;
+#pragma unroll
+              for (int q = 0; q < 4; ++q)
+                *reinterpret_cast<ushort_t*>(sp + q * 128) =
+                    (pos == q) ? gb : (ushort_t)0;
+            }
+          }
+        }
+        __syncthreads();
+        // 256 lines x 8 chunks of 16 B: 8 consecutive lanes store one line
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          int idx = tid + i * NTHREADS;
+          int ch = idx & 7, line = idx >> 3;
+          int q = line & 3, slot = line >> 2;
+          int j = slot % NJ, lr = slot / NJ;
+          int gr = m0 + (lr / PR) * WM + pass * PR + lr % PR;
+          int gcol = n0 + j * 64;
+          if (gr >= p.M || gcol >= p.N) continue;
+          int c0 = gcol % p.Cout, pix = gcol / p.Cout;
+          int wo = pix % p.CWo, ho = pix / p.CWo;
+          size_t o = (((size_t)gr * H2 + ho * 2 + (q >> 1)) * W2 + wo * 2 +
+                      (q & 1)) * p.Cout + c0 + ch * 8;
+          *reinterpret_cast<uint4*>(dact + o) = *reinterpret_cast<const uint4*>(
+              smem + (slot * 4 + q) * 128 + ((ch ^ (((lr >> 2) & 3) << 1)) << 4));
+        }
+      }
+    }
+  }
+  if (!use_lines) {
 #pragma unroll
   for (int mi = 0; mi < MI; ++mi) {
 #pragma unroll
@@ -496,17 +606,110 @@ epilogue:
           }
           if (OUT == OUT_BF16) {
             reinterpret_cast<ushort_t*>(p.C)[(size_t)gr * p.ldc + gc] = f2bf(v);
-          } else if (OUT == OUT_F32_SLICES) {
+          } else if (OUT == OUT_F32_SLICES || OUT == OUT_F32_SLICES_FIX) {
             // split-K without atomics: each k-slice owns a full [M][N]
             // plane; a deterministic epilogue sums the planes (fwd path
             // must be bitwise-reproducible per (seed, step))
             float* outp = reinterpret_cast<float*>(p.C) +
                           (size_t)bz * p.M * p.ldc;
-            outp[(size_t)gr * p.ldc + gc] = v;
+            if (OUT == OUT_F32_SLICES_FIX)  // write through, see below
+              __hip_atomic_store(&outp[(size_t)gr * p.ldc + gc], v,
+                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else
+              outp[(size_t)gr * p.ldc + gc] = v;
           } else {
             atomicAdd(reinterpret_cast<float*>(p.C) + (size_t)gr * p.ldc + gc, v);
           }
         }
+      }
+    }
+  }
+  }  // !use_lines
+  if constexpr (OUT == OUT_F32_SLICES_FIX) {
+    static_assert(BM == 64 && BN == 64, "fix-up thread map is 64 x 64");
+    // Split-K fix-up without a second launch: the block that finishes a
+    // tile LAST (per-tile ticket) sums the planes in slice order 0..sk-1 —
+    // its own plane re-read from memory with the others, so the sum is the
+    // one fwd_epilogue_kernel computes — and writes bias/relu/dropout bf16.
+    // No block waits on another.  The other slices may have run on other
+    // XCDs with their own L2: the plane stores above are agent-scope
+    // (write-through) stores, the block barrier orders them before thread
+    // 0's release fence and ticket, and the last block reads them back with
+    // agent-scope loads behind an acquire fence.  One release fence per
+    // BLOCK: a device-scope fence in every wave of every block writes the
+    // XCD's L2 back 2048 times and cost 60 us at fc1's B=1024 shape.
+    {
+      __shared__ unsigned last_flag;
+      __syncthreads();  // every wave's plane stores are complete
+      unsigned* tk = p.tickets + (size_t)by * gridDim.x + bx;
+      if (tid == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        last_flag = (atomicAdd(tk, 1u) == (unsigned)p.splitk - 1u) ? 1u : 0u;
+      }
+      __syncthreads();
+      if (last_flag) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        const size_t plane = (size_t)p.M * p.ldc;
+        const float* acc0 = reinterpret_cast<const float*>(p.C);
+        const uint64_t off = p.offset_dev ? (uint64_t)*p.offset_dev : p.offset;
+        const int gr = m0 + (tid >> 2);
+        // a thread owns 16 columns of one row as two 8-column halves; the
+        // loads go out four slices (2 x 4 x 4 8-byte loads) at a time so a
+        // tile costs splitk/4 memory round trips, and are added in slice
+        // order (N % 8 == 0 is a host-side condition of this route)
+        const int gcb = n0 + (tid & 3) * 16;
+        const bool ok[2] = {gr < p.M && gcb < p.N, gr < p.M && gcb + 8 < p.N};
+        float sum[2][8];
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+          for (int e = 0; e < 8; ++e) sum[h][e] = 0.f;
+        for (int s0 = 0; s0 < p.splitk; s0 += 4) {
+          union { unsigned long long q; float f[2]; } t[4][2][4];
+#pragma unroll
+          for (int ds = 0; ds < 4; ++ds)
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+              for (int e2 = 0; e2 < 4; ++e2) {
+                t[ds][h][e2].q = 0ull;
+                if (ok[h] && s0 + ds < p.splitk)
+                  t[ds][h][e2].q = __hip_atomic_load(
+                      reinterpret_cast<const unsigned long long*>(
+                          acc0 + (size_t)(s0 + ds) * plane +
+                          (size_t)gr * p.N + gcb + h * 8 + e2 * 2),
+                      __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              }
+#pragma unroll
+          for (int ds = 0; ds < 4; ++ds)
+            if (s0 + ds < p.splitk)
+#pragma unroll
+              for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int e = 0; e < 8; ++e)
+                  sum[h][e] += t[ds][h][e >> 1].f[e & 1];
+        }
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int gc = gcb + h * 8;
+          if (!ok[h]) continue;
+          union { ushort_t u[8]; uint4 v; } o;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const size_t i = (size_t)gr * p.N + gc + e;
+            float v = sum[h][e];
+            v += p.bias[gc + e];
+            if (p.relu) v = v > 0.f ? v : 0.f;
+            if (p.p_keep < 1.0f) {
+              float u = philox_uniform(p.seed, off, (uint64_t)i);
+              v = (u < p.p_keep) ? v / p.p_keep : 0.f;
+            }
+            o.u[e] = f2bf(v);
+          }
+          *reinterpret_cast<uint4*>(p.Y + (size_t)gr * p.N + gc) = o.v;
+        }
+        if (tid == 0)  // self-reset: the next launch finds zeros
+          __hip_atomic_store(tk, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
   }
@@ -575,6 +778,9 @@ GEMM_ENTRY(gemm_fwd_drop_64_bt, 64, 64, A_N, B_NMAJ, EPI_BIAS_RELU_DROP, OUT_BF1
 // split-K fwd slices (grid-starved small-M cases): deterministic planes
 GEMM_ENTRY(gemm_fwd_slices_64, 64, 64, A_N, B_KMAJ, EPI_NONE, OUT_F32_SLICES, 1)
 GEMM_ENTRY(gemm_fwd_slices_64_bt, 64, 64, A_N, B_NMAJ, EPI_NONE, OUT_F32_SLICES, 1)
+// the same with the in-kernel fix-up (needs p.tickets, p.Y, p.relu)
+GEMM_ENTRY(gemm_fwd_slices_fix_64, 64, 64, A_N, B_KMAJ, EPI_NONE, OUT_F32_SLICES_FIX, 1)
+GEMM_ENTRY(gemm_fwd_slices_fix_64_bt, 64, 64, A_N, B_NMAJ, EPI_NONE, OUT_F32_SLICES_FIX, 1)
 // conv gathers: thousands of WGs -> single-buffer, TLP hides latency
 GEMM_ENTRY(conv_fwd_pool, 128, 64, A_CONV_FWD, B_KMAJ, EPI_POOL, OUT_BF16, 0)
 GEMM_ENTRY(conv_fwd_pool_bt, 128, 64, A_CONV_FWD, B_NMAJ, EPI_POOL, OUT_BF16, 0)

@@ -19,6 +19,11 @@ struct GemmParams {
                            // (hipGraph replay: host args are frozen)
   float* db;  // EPI_UNPOOL / EPI_MASK_DB: bias-grad accumulator
   const unsigned short* actm;  // EPI_MASK_DB: saved activation (mask source)
+  int unpool_lines;   // EPI_UNPOOL: stage the tile in LDS, store 128 B lines
+  unsigned* tickets;  // OUT_F32_SLICES_FIX: per-tile counters; the last slice
+                      // of a tile sums the planes and writes bf16 y (p.Y)
+  unsigned short* Y;  // OUT_F32_SLICES_FIX: final bf16 output [M][N]
+  int relu;           // OUT_F32_SLICES_FIX: relu in the fix-up
 };
 
 // gemm_tile.hip — implicit-GEMM MFMA entry points
@@ -42,8 +47,11 @@ void conv_dx_gemm(const GemmParams&, hipStream_t);
 void conv_dw_gemm(const GemmParams&, hipStream_t);
 // dw_tr.hip — glds + ds_read_b64_tr_b16 k-major dW GEMMs (no staging scatter)
 void conv_dw_tr(const GemmParams&, hipStream_t);    // 5x5-SAME gather A
-void gemm_dw_tr_128(const GemmParams&, hipStream_t);  // plain k-major A, BN=128
-void gemm_dw_tr_64(const GemmParams&, hipStream_t);   // plain k-major A, BN=64
+// plain k-major A; tbm, bn in {64, 128}.  single_writer (splitk == 1, C and
+// ldc 16-byte aligned): each output element is read-added-written once by
+// one lane, no atomics
+void gemm_dw_tr(const GemmParams&, int tbm, int bn, bool single_writer,
+                hipStream_t);
 
 // ops_misc.hip — host wrappers
 void launch_relu_drop_bwd(const unsigned short* dy, const unsigned short* y,
@@ -180,6 +188,9 @@ void launch_conv2_dw_slab(const unsigned short* x, const unsigned short* dact,
 // gemm_tile.hip — split-K fwd slice entries + their summing epilogue
 void gemm_fwd_slices_64(const GemmParams&, hipStream_t);
 void gemm_fwd_slices_64_bt(const GemmParams&, hipStream_t);
+// the same with the in-kernel fix-up: needs p.tickets, p.Y, p.relu
+void gemm_fwd_slices_fix_64(const GemmParams&, hipStream_t);
+void gemm_fwd_slices_fix_64_bt(const GemmParams&, hipStream_t);
 // ops_misc.hip — fwd epilogue: y = [drop][relu](sum_slices + bias), bf16
 void launch_fwd_epilogue(const float* acc, const float* bias,
                          unsigned short* y, int M, int N, int slices,
