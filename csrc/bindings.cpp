@@ -898,6 +898,56 @@ void batch_gather(torch::Tensor img_u8, torch::Tensor lab_u8,
                       (uint64_t)step, sd, cur_stream());
 }
 
+void batch_gather_aug(torch::Tensor img_u8, torch::Tensor lab_u8,
+                      torch::Tensor lut, torch::Tensor table, torch::Tensor x,
+                      torch::Tensor y, int64_t seed, int64_t step,
+                      c10::optional<torch::Tensor> step_dev) {
+  CHECK_CUDA(img_u8); CHECK_CONTIG(img_u8);
+  CHECK_CUDA(lab_u8); CHECK_CONTIG(lab_u8);
+  CHECK_CUDA(lut); CHECK_BF16(lut); CHECK_CONTIG(lut);
+  CHECK_CUDA(table); CHECK_CONTIG(table);
+  CHECK_CUDA(x); CHECK_BF16(x); CHECK_CONTIG(x);
+  CHECK_CUDA(y); CHECK_CONTIG(y);
+  TORCH_CHECK(img_u8.scalar_type() == at::kByte &&
+              lab_u8.scalar_type() == at::kByte,
+              "batch_gather_aug: images/labels must be uint8");
+  TORCH_CHECK(y.scalar_type() == at::kLong,
+              "batch_gather_aug: y must be int64");
+  TORCH_CHECK(table.scalar_type() == at::kInt && table.dim() == 2 &&
+              table.size(1) == 6 && table.size(0) >= 1 &&
+              table.size(0) < (int64_t(1) << 31),
+              "batch_gather_aug: table must be int32 [T >= 1, 6]");
+  const int64_t N = lab_u8.numel(), B = y.numel();
+  TORCH_CHECK(N >= 1 && N < (int64_t(1) << 31),
+              "batch_gather_aug: N out of range");
+  TORCH_CHECK(B >= 1 && B <= N, "batch_gather_aug: batch size ", B,
+              " must be in [1, N=", N, "]");
+  TORCH_CHECK(img_u8.numel() == N * 784,
+              "batch_gather_aug: images must be [N,784]");
+  TORCH_CHECK(x.numel() == B * 784,
+              "batch_gather_aug: x must hold B*784 values");
+  TORCH_CHECK(lut.numel() == 256,
+              "batch_gather_aug: lut must have 256 entries");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(img_u8.data_ptr()) % 8 == 0 &&
+              reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "batch_gather_aug: images must be 8B- and x 16B-aligned");
+  const long* sd = nullptr;
+  if (step_dev.has_value() && step_dev->defined()) {
+    TORCH_CHECK(step_dev->is_cuda() && step_dev->scalar_type() == at::kLong &&
+                step_dev->numel() >= 1, "batch_gather_aug: step_dev must be "
+                "a device int64 tensor");
+    sd = step_dev->data_ptr<long>();
+  } else {
+    TORCH_CHECK(step >= 0, "batch_gather_aug: step must be >= 0");
+  }
+  launch_batch_gather_aug(img_u8.data_ptr<uint8_t>(),
+                          lab_u8.data_ptr<uint8_t>(), bf16_ptr(lut),
+                          table.data_ptr<int>(), (uint32_t)table.size(0),
+                          bf16_mut(x), y.data_ptr<long>(), (uint32_t)N,
+                          (uint32_t)B, (uint64_t)seed, (uint64_t)step, sd,
+                          cur_stream());
+}
+
 void range_gather(torch::Tensor img_u8, torch::Tensor lab_u8,
                   torch::Tensor lut, torch::Tensor x, torch::Tensor y,
                   int64_t start, c10::optional<torch::Tensor> start_dev) {
@@ -1075,6 +1125,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("img_u8"), py::arg("lab_u8"), py::arg("lut"), py::arg("x"),
         py::arg("y"), py::arg("seed"), py::arg("step"),
         py::arg("step_dev") = c10::nullopt);
+  m.def("batch_gather_aug", &batch_gather_aug,
+        "batch_gather with on-device affine augmentation: image j is warped "
+        "(integer bilinear, zero background) by row aug_indices(seed, step, "
+        "j) of the int32 [T,6] Q16 inverse-affine table before the LUT",
+        py::arg("img_u8"), py::arg("lab_u8"), py::arg("lut"),
+        py::arg("table"), py::arg("x"), py::arg("y"), py::arg("seed"),
+        py::arg("step"), py::arg("step_dev") = c10::nullopt);
   m.def("range_gather", &range_gather,
         "sequential chunk [start, start+B) of the device-resident uint8 set "
         "(LUT-normalised to bf16) into x [B,28,28,1] bf16 / y [B] int64; "

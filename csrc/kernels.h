@@ -94,6 +94,16 @@ void launch_batch_gather(const uint8_t* img, const uint8_t* lab,
                          const unsigned short* lut, unsigned short* x,
                          long* y, uint32_t N, uint32_t B, uint64_t seed,
                          uint64_t step, const long* step_dev, hipStream_t);
+// the same batch with on-device affine augmentation: image j is warped
+// (integer bilinear, zero background) by row aug_indices(seed, step, j) of
+// the int32 [T,6] Q16 inverse-affine `table` before the LUT.  Memory-safe
+// for any table content; T >= 1.
+void launch_batch_gather_aug(const uint8_t* img, const uint8_t* lab,
+                             const unsigned short* lut, const int* table,
+                             uint32_t T, unsigned short* x, long* y,
+                             uint32_t N, uint32_t B, uint64_t seed,
+                             uint64_t step, const long* step_dev,
+                             hipStream_t);
 // eval_ops.hip — device-side evaluation.  range_gather: the sequential chunk
 // [start, start+B) of the resident set (start from the host or *start_dev),
 // rows past N zero-filled with label -1.  softmax_eval: loss / live / correct

@@ -12,6 +12,14 @@ DataSet.next_batch drops it), epoch 0 unshuffled (as DataSet), later epochs
 ordered by a cycle-walking Feistel permutation keyed on (seed, epoch) —
 ops/cpu_ref.py::feistel_perm.  A resumed run that seeks to its restored step
 therefore sees exactly the batches an uninterrupted run would have seen.
+
+Optional affine augmentation (small random shifts / rotations / scalings)
+runs inside the same gather: a table of T integer inverse-affine maps is
+built once from the data set's seed (ops/cpu_ref.py::augment_table) and
+lives on the device; batch position j at `step` is warped by table row
+aug_indices(seed, step, j), again a pure function of (seed, step), so resume
+and hipGraph capture keep working unchanged.  Evaluation (range_into) never
+augments.
 """
 
 from __future__ import annotations
@@ -22,6 +30,7 @@ import numpy as np
 import torch
 
 from ..ops import functional as Fx
+from ..ops.cpu_ref import augment_table
 from .mnist_data import (IMAGE_SIZE, NUM_CHANNELS, PIXEL_DEPTH, TEST_IMAGES,
                          TEST_LABELS, TRAIN_IMAGES, TRAIN_LABELS,
                          extract_images_u8, extract_labels)
@@ -40,11 +49,18 @@ class DeviceDataSet:
 
     images_u8: [N, 784] (or [N,28,28[,1]]) uint8; labels: [N] integer < 256.
     Sharding follows DataSet: rank::world slices unless shard=False.
+
+    Augmentation: any of augment_shift (px) / augment_rotate (deg) /
+    augment_scale (frac) above 0 builds a table of augment_table_size
+    transforms from `seed`; a ready int32 [T,6] `aug_table` takes precedence.
     """
 
     def __init__(self, images_u8, labels_u8, worker_id: int = 0,
                  n_workers: int = 1, shard: bool = True, seed: int = 0,
-                 device="cpu", dtype: torch.dtype = torch.float32):
+                 device="cpu", dtype: torch.dtype = torch.float32,
+                 augment_shift: float = 0.0, augment_rotate: float = 0.0,
+                 augment_scale: float = 0.0, augment_table_size: int = 4096,
+                 aug_table=None):
         images_u8 = np.asarray(images_u8)
         labels_u8 = np.asarray(labels_u8)
         if images_u8.dtype != np.uint8:
@@ -66,6 +82,23 @@ class DeviceDataSet:
             np.array(labels_u8, dtype=np.uint8)).to(self.device)
         self._lut = normalisation_lut(dtype).to(self.device)
         self._cursor = 0
+        if aug_table is None and max(augment_shift, augment_rotate,
+                                     augment_scale) > 0:
+            aug_table = augment_table(augment_table_size, self.seed,
+                                      augment_shift, augment_rotate,
+                                      augment_scale)
+        self._aug_table = None
+        if aug_table is not None:
+            tab = torch.as_tensor(np.asarray(aug_table))
+            if tab.dtype != torch.int32 or tab.dim() != 2 \
+                    or tab.shape[1] != 6 or tab.shape[0] < 1:
+                raise ValueError("aug_table must be int32 [T >= 1, 6]")
+            self._aug_table = tab.contiguous().to(self.device)
+
+    @property
+    def aug_table(self):
+        """int32 [T,6] on the device, or None when augmentation is off."""
+        return self._aug_table
 
     @property
     def images(self):
@@ -85,13 +118,15 @@ class DeviceDataSet:
 
     # -- stateless access ------------------------------------------------
     def gather_into(self, x: torch.Tensor, y: torch.Tensor, step=None,
-                    step_dev=None):
+                    step_dev=None, augment: bool = True):
         """Write the batch at `step` (host int) or `*step_dev` (device
-        int64; capturable into a hipGraph) into x [B,28,28,1] / y [B]."""
+        int64; capturable into a hipGraph) into x [B,28,28,1] / y [B],
+        augmented when the data set has a table (augment=False: raw)."""
         if x.dtype != self.dtype:
             raise TypeError(f"x is {x.dtype}, data set built for {self.dtype}")
         return Fx.batch_gather(self._images, self._labels, self._lut, x, y,
-                               self.seed, step=step, step_dev=step_dev)
+                               self.seed, step=step, step_dev=step_dev,
+                               aug_table=self._aug_table if augment else None)
 
     def range_into(self, x: torch.Tensor, y: torch.Tensor, start=None,
                    start_dev=None):
@@ -108,7 +143,7 @@ class DeviceDataSet:
     @classmethod
     def random(cls, n: int, seed: int, device="cpu",
                dtype: torch.dtype = torch.float32, worker_id: int = 0,
-               n_workers: int = 1):
+               n_workers: int = 1, **augment):
         """Seeded uint8 stand-in (uniform pixels, labels in [0, 10)) for
         runs without idx-gz files."""
         rng = np.random.RandomState(seed)
@@ -116,18 +151,19 @@ class DeviceDataSet:
                           dtype=np.uint8)
         lab = rng.randint(0, 10, size=n, dtype=np.uint8)
         return cls(img, lab, worker_id=worker_id, n_workers=n_workers,
-                   seed=seed, device=device, dtype=dtype)
+                   seed=seed, device=device, dtype=dtype, **augment)
 
-    def batch_at(self, step: int, batch_size: int):
+    def batch_at(self, step: int, batch_size: int, augment: bool = True):
         """(x, y) of the batch at `step` — a pure function of its arguments
-        (and the seed)."""
+        (and the seed).  augment=False gives the raw batch of an augmented
+        data set."""
         if batch_size > self._num_examples:
             raise ValueError(f"batch size {batch_size} exceeds the "
                              f"{self._num_examples} examples of this rank")
         x = torch.empty((batch_size, IMAGE_SIZE, IMAGE_SIZE, NUM_CHANNELS),
                         dtype=self.dtype, device=self.device)
         y = torch.empty(batch_size, dtype=torch.int64, device=self.device)
-        return self.gather_into(x, y, step=int(step))
+        return self.gather_into(x, y, step=int(step), augment=augment)
 
     # -- DataSet-style cursor ---------------------------------------------
     def seek(self, step: int):
@@ -142,11 +178,12 @@ class DeviceDataSet:
 def load_device_mnist(data_dir: str, subset: int = 0, worker_id: int = 0,
                       n_workers: int = 1, shard: bool = True, seed: int = 0,
                       device="cpu", dtype: torch.dtype = torch.float32,
-                      split: str = "train"):
+                      split: str = "train", **augment):
     """idx-gz train files -> DeviceDataSet holding exactly the examples the
     host-fed path (engine/train.py::make_dataset) trains on: the rank::world
     shard unless shard=False, then `subset` keeps its first N examples.
-    split="test" reads the t10k pair instead, same shard/subset rules."""
+    split="test" reads the t10k pair instead, same shard/subset rules.
+    **augment: DeviceDataSet's augmentation arguments, passed through."""
     if split not in ("train", "test"):
         raise ValueError(f"split must be 'train' or 'test', not {split!r}")
     names = ((TRAIN_IMAGES, TRAIN_LABELS) if split == "train"
@@ -165,4 +202,4 @@ def load_device_mnist(data_dir: str, subset: int = 0, worker_id: int = 0,
     if subset:
         images, labels = images[:subset], labels[:subset]
     return DeviceDataSet(images, labels, shard=False, seed=seed,
-                         device=device, dtype=dtype)
+                         device=device, dtype=dtype, **augment)

@@ -541,13 +541,29 @@ def make_dataset(flags, rank: int, world: int, device, dtype):
         log.info("--device_data has no effect with --synthetic_data / "
                  "--fake_data")
         device_data = False
+    augment = {k: getattr(flags, k, 0) or 0 for k in
+               ("augment_shift", "augment_rotate", "augment_scale")}
+    if min(augment.values()) < 0:
+        raise ValueError(f"augmentation magnitudes must be >= 0: {augment}")
+    augmented = max(augment.values()) > 0
+    if augmented and not device_data:
+        raise ValueError(
+            "--augment_shift/--augment_rotate/--augment_scale need an "
+            "effective --device_data (idx-gz files, not --synthetic_data / "
+            "--fake_data): augmentation runs inside the resident gather and "
+            "the host-fed and synthetic paths have none")
     if device_data:
         from ..data import load_device_mnist
+        if augmented:
+            augment["augment_table_size"] = \
+                getattr(flags, "augment_table", 0) or 4096
+        else:
+            augment = {}
         return load_device_mnist(flags.data_dir, subset=flags.subset,
                                  worker_id=rank, n_workers=world,
                                  shard=not flags.no_shard,
                                  seed=flags.seed + rank, device=device,
-                                 dtype=dtype)
+                                 dtype=dtype, **augment)
     if flags.synthetic_data:
         pool = max(4 * flags.batch_size, 8192)
         return SyntheticDataSet(pool_size=pool, device=device, dtype=dtype,

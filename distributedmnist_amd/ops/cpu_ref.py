@@ -256,12 +256,127 @@ def batch_indices(n: int, batch_size: int, seed: int, step: int):
     return feistel_perm(n, seed, epoch, p)
 
 
-def batch_gather(img_u8, lab_u8, lut, x, y, seed: int, step: int):
+# -- affine augmentation (integer only; csrc/data_gather.hip mirrors it) -----
+#
+# A transform table is int32 [T, 6]: rows (a00, a01, a10, a11, t0, t1) in
+# Q16, the INVERSE map (output pixel -> source position) about the image
+# centre (13.5, 13.5):
+#
+#   src_col = 13.5 + a00 (c - 13.5) + a01 (r - 13.5) + t0
+#   src_row = 13.5 + a10 (c - 13.5) + a11 (r - 13.5) + t1
+#
+# evaluated in Q17 on the doubled coordinates uc = 2c - 27, ur = 2r - 27 so
+# that the half-pixel centre stays an integer.  The bilinear weights keep 8
+# fractional bits; pixels outside the image are background byte 0.
+
+AUG_ONE = 1 << 16
+AUG_IDENTITY = (AUG_ONE, 0, 0, AUG_ONE, 0, 0)
+AUG_MAX_A = 4 * AUG_ONE     # |a| bound the builder guarantees
+AUG_MAX_T = 64 * AUG_ONE    # |t| bound the builder guarantees
+_SIDE = 28
+
+
+def augment_table(T: int, seed: int, shift_px: float = 0.0,
+                  rotate_deg: float = 0.0, scale_frac: float = 0.0):
+    """Seeded table of T random inverse affine maps -> int32 numpy [T, 6].
+    Angle uniform in +-rotate_deg, scale log-uniform in [1/(1+scale_frac),
+    1+scale_frac], translation uniform real in +-shift_px per axis; each
+    entry is the inverse of rotate o scale (plus the translation of the
+    source position), rounded to nearest.  All-zero magnitudes give the
+    identity everywhere.  Arguments that could leave |a| <= 4 or |t| <= 64
+    (in pixels) are rejected: inside those bounds the Q17 coordinates of
+    affine_warp_u8 cannot overflow int32."""
+    import numpy as np
+    T = int(T)
+    if T < 1:
+        raise ValueError("augment_table: T must be >= 1")
+    for name, v, hi in (("shift_px", shift_px, 64.0),
+                        ("rotate_deg", rotate_deg, 180.0),
+                        ("scale_frac", scale_frac, 3.0)):
+        if not (0.0 <= float(v) <= hi):  # NaN fails both compares
+            raise ValueError(f"augment_table: {name}={v} outside [0, {hi}]")
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    rng = np.random.RandomState([seed & _M32, seed >> 32, 0xA0F1])
+    theta = np.deg2rad(rng.uniform(-rotate_deg, rotate_deg, size=T))
+    ls = np.log1p(float(scale_frac))
+    inv_s = np.exp(-rng.uniform(-ls, ls, size=T))
+    t = rng.uniform(-shift_px, shift_px, size=(T, 2))
+    co, si = np.cos(theta) * inv_s, np.sin(theta) * inv_s
+    # inverse of s*R(theta) is (1/s)*R(-theta)
+    tab = np.stack([co, si, -si, co, t[:, 0], t[:, 1]], axis=1) * AUG_ONE
+    tab = np.rint(tab).astype(np.int64)
+    assert np.abs(tab[:, :4]).max() <= AUG_MAX_A
+    assert np.abs(tab[:, 4:]).max() <= AUG_MAX_T
+    return tab.astype(np.int32)
+
+
+def aug_indices(T: int, seed: int, step: int, b: int):
+    """Table row of batch position j at `step` -> int64 numpy [b] in [0, T):
+    a pure function of (seed, step, j) that takes the full 64-bit step.
+    Keyed on the batch POSITION, not on the sample index, so an image meets
+    a different transform in every epoch."""
+    import numpy as np
+    T, step = int(T), int(step)
+    if T < 1:
+        raise ValueError("aug_indices: T must be >= 1")
+    if step < 0:
+        raise ValueError("step must be >= 0")
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    base = _mix32((seed & _M32) ^ _mix32(((seed >> 32) + 0x9E3779B9) & _M32))
+    lo, hi = step & _M32, (step >> 32) & _M32
+    k = _mix32((base + 0x632BE5AB + lo * 0x9E3779B1) & _M32)
+    k = _mix32(k ^ _mix32((hi + 0x7F4A7C15) & _M32))
+    j = np.arange(int(b), dtype=np.uint64)
+    r = _mix32((np.uint64(k) + j * np.uint64(0x85EBCA6B)) & np.uint64(_M32))
+    return (r % np.uint64(T)).astype(np.int64)
+
+
+def affine_warp_u8(rows_u8, entries):
+    """Integer bilinear warp of uint8 images.  rows_u8: [b, 784] uint8,
+    entries: [b, 6] integer (one table row per image) -> uint8 [b, 784].
+    Defined for entries within the builder's bounds (int64 here; the kernel's
+    int32 arithmetic agrees there)."""
+    b = rows_u8.shape[0]
+    dev = rows_u8.device
+    e = entries.to(device=dev, dtype=torch.int64).view(b, 6, 1, 1)
+    u = 2 * torch.arange(_SIDE, device=dev, dtype=torch.int64) - (_SIDE - 1)
+    uc, ur = u.view(1, 1, _SIDE), u.view(1, _SIDE, 1)
+    half = (_SIDE - 1) * AUG_ONE
+    SX = half + e[:, 0] * uc + e[:, 1] * ur + 2 * e[:, 4]
+    SY = half + e[:, 2] * uc + e[:, 3] * ur + 2 * e[:, 5]
+    x0, y0 = SX >> 17, SY >> 17  # arithmetic shift = floor
+    fx, fy = (SX >> 9) & 255, (SY >> 9) & 255
+    src = rows_u8.reshape(b, _SIDE * _SIDE).long()
+
+    def tap(yy, xx):
+        ok = (xx >= 0) & (xx < _SIDE) & (yy >= 0) & (yy < _SIDE)
+        flat = yy.clamp(0, _SIDE - 1) * _SIDE + xx.clamp(0, _SIDE - 1)
+        v = src.gather(1, flat.view(b, -1)).view(b, _SIDE, _SIDE)
+        return torch.where(ok, v, torch.zeros_like(v))
+
+    top = tap(y0, x0) * (256 - fx) + tap(y0, x0 + 1) * fx
+    bot = tap(y0 + 1, x0) * (256 - fx) + tap(y0 + 1, x0 + 1) * fx
+    v = (top * (256 - fy) + bot * fy + 32768) >> 16
+    return v.to(torch.uint8).view(b, _SIDE * _SIDE)
+
+
+def batch_gather(img_u8, lab_u8, lut, x, y, seed: int, step: int,
+                 aug_table=None):
     """x[j] = lut[img_u8[idx[j]]], y[j] = lab_u8[idx[j]] written into the
-    caller's buffers (any device; x takes lut's dtype)."""
+    caller's buffers (any device; x takes lut's dtype).  With `aug_table`
+    (int32 [T, 6]) row j is warped by table entry aug_indices(...)[j]
+    between the permutation and the LUT; labels are unchanged."""
     n, b = lab_u8.shape[0], y.shape[0]
     idx = torch.from_numpy(batch_indices(n, b, seed, step)).to(img_u8.device)
-    x.copy_(lut[img_u8[idx].long()].reshape(x.shape))
+    rows = img_u8[idx]
+    if aug_table is not None:
+        if aug_table.dim() != 2 or aug_table.shape[1] != 6 \
+                or aug_table.shape[0] < 1:
+            raise ValueError("aug_table must be [T >= 1, 6]")
+        t = torch.from_numpy(aug_indices(aug_table.shape[0], seed, step, b))
+        rows = affine_warp_u8(rows.reshape(b, -1),
+                              aug_table[t.to(aug_table.device)])
+    x.copy_(lut[rows.long()].reshape(x.shape))
     y.copy_(lab_u8[idx].long())
     return x, y
 

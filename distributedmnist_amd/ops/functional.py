@@ -194,29 +194,43 @@ def grad_mask(grad: torch.Tensor, keep: float, seed: int, step: int,
 
 def batch_gather(img_u8: torch.Tensor, lab_u8: torch.Tensor,
                  lut: torch.Tensor, x: torch.Tensor, y: torch.Tensor,
-                 seed: int, step: int | None = None, step_dev=None):
+                 seed: int, step: int | None = None, step_dev=None,
+                 aug_table: torch.Tensor | None = None):
     """Build the batch at `step` from the resident uint8 training set into
     the caller's buffers: x[j] = lut[img[perm(...)]] ([B,28,28,1], lut's
     dtype), y[j] = labels ([B] int64).  The sample order is a pure function
     of (seed, step) — ops/cpu_ref.py::batch_indices.  Exactly one of `step`
     (host int) / `step_dev` (device int64, hipGraph-capturable on the HIP
-    path) is given."""
+    path) is given.  With `aug_table` (int32 [T,6], ops/cpu_ref.py::
+    augment_table) image j is warped by table row aug_indices(seed, step, j)
+    before the LUT (batch_gather_aug_kernel on the HIP path); without it the
+    plain kernel runs."""
     if (step is None) == (step_dev is None):
         raise ValueError("batch_gather: pass exactly one of step / step_dev")
     if y.shape[0] > lab_u8.shape[0]:
         raise ValueError(f"batch size {y.shape[0]} exceeds the "
                          f"{lab_u8.shape[0]} examples of this rank")
+    if aug_table is not None and (
+            aug_table.dtype != torch.int32 or aug_table.dim() != 2
+            or aug_table.shape[1] != 6 or aug_table.shape[0] < 1):
+        raise ValueError("batch_gather: aug_table must be int32 [T >= 1, 6]")
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     if _use_hip(x):
         if seed >= 1 << 63:
             seed -= 1 << 64  # int64 carrier of the same 64 bits
-        _C.ext().batch_gather(img_u8, lab_u8, lut, x, y, seed,
-                              0 if step is None else int(step),
-                              step_dev=step_dev)
+        if aug_table is None:
+            _C.ext().batch_gather(img_u8, lab_u8, lut, x, y, seed,
+                                  0 if step is None else int(step),
+                                  step_dev=step_dev)
+        else:
+            _C.ext().batch_gather_aug(img_u8, lab_u8, lut, aug_table, x, y,
+                                      seed, 0 if step is None else int(step),
+                                      step_dev=step_dev)
     else:
         if step is None:
             step = int(step_dev.item())  # reference path: host sync is fine
-        cpu_ref.batch_gather(img_u8, lab_u8, lut, x, y, seed, int(step))
+        cpu_ref.batch_gather(img_u8, lab_u8, lut, x, y, seed, int(step),
+                             aug_table=aug_table)
     return x, y
 
 

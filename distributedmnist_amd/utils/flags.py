@@ -92,6 +92,20 @@ def build_train_parser() -> argparse.ArgumentParser:
                         "when the step is captured); the batch order is a "
                         "pure function of (seed, rank, step). No effect "
                         "with --synthetic_data / --fake_data")
+    p.add_argument("--augment_shift", type=float, default=0.0, metavar="PX",
+                   help=">0 (with --device_data): random translation of "
+                        "every training image by up to PX pixels per axis, "
+                        "inside the resident gather; the transform is a pure "
+                        "function of (seed, rank, step, batch position)")
+    p.add_argument("--augment_rotate", type=float, default=0.0, metavar="DEG",
+                   help=">0 (with --device_data): random rotation by up to "
+                        "DEG degrees about the image centre")
+    p.add_argument("--augment_scale", type=float, default=0.0, metavar="FRAC",
+                   help=">0 (with --device_data): random log-uniform scaling "
+                        "in [1/(1+FRAC), 1+FRAC]")
+    p.add_argument("--augment_table", type=int, default=4096, metavar="T",
+                   help="number of distinct random transforms the augmented "
+                        "gather draws from (built once per rank)")
     p.add_argument("--eval_every_steps", type=int, default=0,
                    help=">0: keep the test set on the device and evaluate it "
                         "every N steps (and after the last step); the step "

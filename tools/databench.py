@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """Real-data input-pipeline benchmark (bench.py measures --synthetic_data
 only).  Generates MNIST-sized idx-gz files from a seed, then times one
-LeNet training step fed four ways, per batch size:
+LeNet training step fed five ways, per batch size:
 
   a  host    DataSet.next_batch -> Trainer.to_device -> graph_or_eager_step
   b  eager   --device_data --hip_graph off  (resident_step, eager gather)
   c  graph   --device_data                  (gather captured in the hipGraph)
   d  synth   --synthetic_data               (graph; device slices + 2 copies)
+  e  augment --device_data --augment_shift 2 --augment_rotate 10
+             --augment_scale 0.1            (graph; warped gather captured)
 
 Every variant is warmed up at its shape, then timed over `--steps` steps
 between two device events with ONE synchronise at the end and no per-step
@@ -30,6 +32,9 @@ VARIANTS = {
     "b": ("device_data_eager", ["--device_data", "--hip_graph", "off"]),
     "c": ("device_data_graph", ["--device_data"]),
     "d": ("synthetic_graph", ["--synthetic_data"]),
+    "e": ("device_data_augment_graph",
+          ["--device_data", "--augment_shift", "2", "--augment_rotate", "10",
+           "--augment_scale", "0.1"]),
 }
 
 
@@ -82,7 +87,7 @@ def spread(xs):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--batch_sizes", default="64,1024")
-    ap.add_argument("--variants", default="a,b,c,d")
+    ap.add_argument("--variants", default="a,b,c,d,e")
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=5)
@@ -127,7 +132,7 @@ def main():
                     ips[k].append(round(
                         bs * args.steps / timed(steps_fn[k], args.steps), 1))
             entry = {k: dict(spread(v), runs=v) for k, v in ips.items()}
-            for num, den in (("c", "a"), ("c", "d")):
+            for num, den in (("c", "a"), ("c", "d"), ("e", "c")):
                 if num in ips and den in ips:
                     entry[f"{num}/{den}"] = spread(
                         [round(x / y, 4) for x, y in zip(ips[num], ips[den])])
