@@ -563,6 +563,52 @@ torch::Tensor linear_dx_unpool(torch::Tensor dyeff, torch::Tensor w,
   return dact;
 }
 
+// 128-tile threshold of linear_dx_pooled, in 128 x 128 tiles.  Swept solo at
+// fc1's 3136 x 512 (64-tile / 128-tile us): B=512 (100 tiles) 21.1 / 23.7,
+// B=640 (125) 24.2 / 24.9, B=768 (150) 26.6 / 26.2, B=1024 (200) 32.1 / 28.8,
+// B=2048 (400) 55.4 / 39.9.  linear_dx_unpool's 400 was set by its 4x larger
+// write burst, which this epilogue does not have.
+#define POOLED_DX_BIG_TILES 150
+
+torch::Tensor linear_dx_pooled(torch::Tensor dyeff, torch::Tensor w,
+                               torch::Tensor amax, torch::Tensor db_out,
+                               int64_t Ho, int64_t Wo, int64_t C,
+                               int64_t tile) {
+  // gp = mask(dyeff @ W^T): linear_dx_unpool without the scatter.  The dX
+  // rows are pooled [Ho][Wo][C] features; the epilogue zeroes the dead
+  // windows (amax byte >= 4), accumulates the conv bias grad and stores the
+  // POOLED gradient [B][Ho][Wo][C].  The pre-pool dact (4x the bytes, 75 %
+  // zeros) is never written: conv_dx_pooled / conv_dw_pooled_into rebuild it
+  // in LDS from (gp, amax).  tile = 64 | 128 forces a tile, 0 = by grid size.
+  CHECK_BF16(dyeff); CHECK_CONTIG(dyeff); CHECK_BF16(w); CHECK_CONTIG(w);
+  CHECK_CONTIG(amax);
+  TORCH_CHECK(amax.scalar_type() == at::kByte, "amax must be uint8");
+  int B = dyeff.size(0), N = dyeff.size(1), K = w.size(0);
+  TORCH_CHECK(K == Ho * Wo * C, "linear_dx_pooled: K != Ho*Wo*C");
+  TORCH_CHECK(w.size(1) == N, "linear_dx_pooled: w is [K][N]");
+  TORCH_CHECK(amax.numel() == (int64_t)B * K, "linear_dx_pooled: amax shape");
+  TORCH_CHECK(tile == 0 || tile == 64 || tile == 128,
+              "linear_dx_pooled: tile is 0, 64 or 128");
+  auto gp = torch::empty({B, (int)Ho, (int)Wo, (int)C}, dyeff.options());
+  GemmParams p{};
+  p.A = bf16_ptr(dyeff); p.B = bf16_ptr(w);
+  p.C = gp.data_ptr();
+  p.M = B; p.N = K; p.K = N;
+  p.lda = N; p.ldb = N; p.ldc = K;
+  p.splitk = 1;
+  p.CHo = Ho; p.CWo = Wo; p.Cout = C;
+  p.amax = amax.data_ptr<uint8_t>();
+  p.db = db_out.defined() ? db_out.data_ptr<float>() : nullptr;
+  // row stores (16 B per lane) need whole 16-column chunks and aligned rows;
+  // anything else takes the per-element epilogue
+  p.unpool_lines = K % 16 == 0 && ((uintptr_t)p.amax & 15) == 0 &&
+                   ((uintptr_t)p.C & 15) == 0;
+  bool big = cdiv(B, 128) * cdiv(K, 128) >= POOLED_DX_BIG_TILES;
+  if (tile) big = tile == 128;
+  (big ? gemm_dx_poolmask_128 : gemm_dx_poolmask_64)(p, cur_stream());
+  return gp;
+}
+
 torch::Tensor linear_dx_mask(torch::Tensor dyeff, torch::Tensor w,
                              torch::Tensor actm, torch::Tensor db_out,
                              double p_keep) {
@@ -702,6 +748,54 @@ torch::Tensor conv_dx(torch::Tensor dact, torch::Tensor w, int64_t Cin) {
     conv_dx_gemm(p, s);
   }
   return dx;
+}
+
+// conv2 backward from the pooled gradient gp [NB][7][7][64] and the pool
+// argmax bytes am: pool2 backward happens in the consumers' LDS staging and
+// the dense dact [NB][14][14][64] never exists in memory.
+static void check_pooled(const torch::Tensor& gp, const torch::Tensor& am) {
+  CHECK_CUDA(gp); CHECK_BF16(gp); CHECK_CONTIG(gp);
+  CHECK_CUDA(am); CHECK_CONTIG(am);
+  TORCH_CHECK(am.scalar_type() == at::kByte, "am must be uint8");
+  TORCH_CHECK(gp.dim() == 4 && gp.size(1) == 7 && gp.size(2) == 7 &&
+                  gp.size(3) == 64,
+              "pooled conv2 backward: gp is [NB][7][7][64]");
+  TORCH_CHECK(am.numel() == gp.numel(), "am / gp shape mismatch");
+  TORCH_CHECK(((uintptr_t)gp.data_ptr() & 15) == 0 &&
+                  ((uintptr_t)am.data_ptr() & 7) == 0,
+              "pooled conv2 backward: gp 16 B / am 8 B alignment");
+}
+
+torch::Tensor conv_dx_pooled(torch::Tensor gp, torch::Tensor am,
+                             torch::Tensor w, int64_t Cin, int64_t force_db) {
+  check_pooled(gp, am);
+  CHECK_BF16(w); CHECK_CONTIG(w);
+  TORCH_CHECK(Cin == 32 && w.numel() == 25 * 32 * 64,
+              "conv_dx_pooled: LeNet conv2 shapes only");
+  TORCH_CHECK(force_db >= 0 && force_db <= 2, "force_db is 0, 1 or 2");
+  int NB = gp.size(0);
+  auto dx = torch::empty({NB, 14, 14, 32}, gp.options());
+  if (NB > 0)
+    launch_conv_dx_slab_pooled(bf16_ptr(gp), am.data_ptr<uint8_t>(),
+                               bf16_ptr(w), bf16_mut(dx), NB, (int)force_db,
+                               cur_stream());
+  return dx;
+}
+
+void conv_dw_pooled_into(torch::Tensor x, torch::Tensor gp, torch::Tensor am,
+                         torch::Tensor dw_out) {
+  check_pooled(gp, am);
+  CHECK_CUDA(x); CHECK_BF16(x); CHECK_CONTIG(x);
+  CHECK_F32(dw_out); CHECK_CONTIG(dw_out);
+  TORCH_CHECK(x.dim() == 4 && x.size(0) == gp.size(0) && x.size(1) == 14 &&
+                  x.size(2) == 14 && x.size(3) == 32,
+              "conv_dw_pooled_into: x is [NB][14][14][32]");
+  TORCH_CHECK(dw_out.numel() == 25 * 32 * 64, "conv_dw_pooled_into: dw size");
+  TORCH_CHECK(((uintptr_t)x.data_ptr() & 15) == 0, "x 16 B alignment");
+  launch_conv2_dw_slab_pooled(bf16_ptr(x), bf16_ptr(gp),
+                              am.data_ptr<uint8_t>(),
+                              dw_out.data_ptr<float>(), (int)x.size(0),
+                              cur_stream());
 }
 
 // --------------------------------------------------------------------------
@@ -1069,6 +1163,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "dx GEMM fused with maxpool2x2 backward scatter + conv db",
         py::arg("dyeff"), py::arg("w"), py::arg("amax"),
         py::arg("db_out"), py::arg("Ho"), py::arg("Wo"), py::arg("C"));
+  m.def("linear_dx_pooled", &linear_dx_pooled,
+        "dx GEMM masked by the pool argmax byte + conv db: pooled gradient",
+        py::arg("dyeff"), py::arg("w"), py::arg("amax"),
+        py::arg("db_out"), py::arg("Ho"), py::arg("Wo"), py::arg("C"),
+        py::arg("tile") = 0);
+  m.def("linear_dx_pooled_tile", [](int64_t B, int64_t K) {
+          return (int64_t)(cdiv((int)B, 128) * cdiv((int)K, 128) >=
+                                   POOLED_DX_BIG_TILES ? 128 : 64);
+        }, "tile linear_dx_pooled picks for dyeff[B,*], w[K,*]");
+  m.def("conv_dx_pooled", &conv_dx_pooled,
+        "conv2 dX from the pooled gradient + pool argmax bytes",
+        py::arg("gp"), py::arg("am"), py::arg("w"), py::arg("Cin"),
+        py::arg("force_db") = 0);
+  m.def("conv_dw_pooled_into", &conv_dw_pooled_into,
+        "conv2 dW from the pooled gradient + pool argmax bytes, into bucket",
+        py::arg("x"), py::arg("gp"), py::arg("am"), py::arg("dw_out"));
   m.def("linear_dw_plan", [](int64_t K, int64_t N, int64_t B) {
     DwPlan pl = linear_dw_plan((int)K, (int)N, (int)B);
     return std::make_tuple(pl.tbm, pl.bn, pl.splitk);

@@ -100,6 +100,20 @@ DEV short8 pack_wait(uint2 lo, uint2 hi) {
   return r.s;
 }
 
+// maxpool-2x2 backward of one (window, 8-channel chunk): the 8 pooled-gradient
+// values g whose argmax byte (a: 8 bytes, channel e in byte e) names window
+// position pos = row*2 + col, zero elsewhere.  Bytes outside 0..3 (7 = dead
+// window) match no position.  The byte is only compared, never an address.
+DEV short8 pool_bwd_select(short8 g, uint2 a, int pos) {
+  short8 v;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    unsigned b = ((e < 4 ? a.x : a.y) >> (8 * (e & 3))) & 0xffu;
+    v[e] = b == (unsigned)pos ? g[e] : (short)0;
+  }
+  return v;
+}
+
 // packed bf16 dot product: c += a.x*b.x + a.y*b.y (v_dot2c_f32_bf16,
 // 2 MACs/cycle/lane — 2x the fp32 FMA rate)
 typedef short bf16x2_t __attribute__((__vector_size__(2 * sizeof(short))));

@@ -67,6 +67,27 @@
 // staged under image g's MFMAs, 88 KB LDS, 1 block/CU) were measured and
 // lose at every G; they stay instantiated for tools/conv2_dw_sweep.py.
 // Numbers: profiles/conv2_dw_slab_b1024_b8192.md.
+//
+// POOLED (KHB = 1, NBUF = 1 only).  `dact` is the pooled gradient gp
+// [NB][7][7][64] and `am` the pool argmax bytes of the same shape; the dense
+// pre-pool gradient exists only in D.  X is staged by glds as above.  D's 28
+// glds jobs are replaced by 392 (window, 8-channel chunk) jobs over the 256
+// lanes: one 16 B load of gp, one 8 B load of am, and for each of the four
+// window positions k = (2wy+rr)*16 + 2wx+cc one 16 B LDS write of
+// (am[e] == rr*2+cc ? gp[e] : 0) at D + k*128 + ((chunk ^ c2_dswz(k)) << 4)
+// — the swizzle moves from the glds source side to the LDS destination, the
+// tr16 fragment addresses do not change.
+//   * Coverage.  49 windows x 4 positions are the 196 real rows k (h, w <=
+//     13), 8 chunks each: every real byte of D is rewritten, zeros included,
+//     with every image, so nothing is stale.
+//   * Padding rows k = h*16 + 14, 15 are never touched by the decode (2wx+cc
+//     <= 13); they are zero-filled ONCE per block before the first barrier.
+//     The w = 14, 15 argument above then holds unchanged: D[k] is an exact
+//     zero, X[s] is finite staged data (glds from the image or the zero
+//     page), the product is an exact zero.
+//   * Bounds.  k <= 13*16 + 13 = 221 < 224 rows; chunk ^ swz < 8; the global
+//     reads are win*64 + chunk*8 + 0..7 < 3136 inside this image.  am only
+//     feeds a compare, so any byte value is memory-safe (non-0..3 = dead).
 
 #include "common.h"
 #include "kernels.h"
@@ -76,6 +97,7 @@
 #define C2_MG 8            // margin pixels in front of / behind the X slab
 #define C2_XIMG (14 * 14 * 32)
 #define C2_DIMG (14 * 14 * 64)
+#define C2_PIMG (7 * 7 * 64)   // pooled gradient / argmax bytes per image
 
 static __device__ __align__(16) unsigned short c2_zero_page[8];  // zero-init
 
@@ -84,14 +106,16 @@ DEV int c2_dswz(int k) { return (((k >> 1) & 1) | (((k >> 3) & 1) << 1)) << 1; }
 
 extern __shared__ __align__(16) ushort_t c2_lds[];
 
-template <int KHB, int NBUF>
+template <int KHB, int NBUF, bool POOLED = false>
 __global__ __launch_bounds__(256, (KHB == 1 && NBUF == 1) ? 3 : 1)
 void conv2_dw_slab_kernel(const ushort_t* __restrict__ x,
                           const ushort_t* __restrict__ dact,
-                          float* __restrict__ dw, int NB, int G) {
+                          float* __restrict__ dw, int NB, int G,
+                          const uint8_t* __restrict__ am) {
+  static_assert(!POOLED || (KHB == 1 && NBUF == 1), "pooled: shipped form only");
   constexpr int NRX = 13 + KHB;                   // X slab rows
   constexpr int XPIX = C2_MG + NRX * 16 + C2_MG;  // X slab pixels
-  constexpr int NJOB = NRX + 28;                  // glds per image
+  constexpr int NJOB = POOLED ? NRX : NRX + 28;   // glds per image
   constexpr int NQ = (NJOB + 3) / 4;              // glds per wave per image
   constexpr int NKB = 5 / KHB;                    // blocks per image group
   constexpr int KS_UNROLL = KHB == 1 ? 7 : 1;
@@ -116,6 +140,13 @@ void conv2_dw_slab_kernel(const ushort_t* __restrict__ x,
     int t = tid & 63;
     int o = (t < 32) ? t * 8 : (C2_MG + NRX * 16) * 32 + (t - 32) * 8;
     *reinterpret_cast<short8*>(X + (tid >> 6) * BUF + o) =
+        short8{0, 0, 0, 0, 0, 0, 0, 0};
+  }
+
+  // POOLED: columns 14, 15 of every D row, zero for the whole block
+  if (POOLED && tid < 224) {
+    int k = (tid >> 4) * 16 + 14 + ((tid >> 3) & 1);
+    *reinterpret_cast<short8*>(D + k * 64 + (tid & 7) * 8) =
         short8{0, 0, 0, 0, 0, 0, 0, 0};
   }
 
@@ -197,6 +228,37 @@ void conv2_dw_slab_kernel(const ushort_t* __restrict__ x,
     if (NBUF == 1) {
       __syncthreads();  // previous image's fragment reads done
       issue(0, img0 + g);
+      if (POOLED) {
+        const ushort_t* gi = dact + (size_t)(img0 + g) * C2_PIMG;
+        const uint8_t* ai = am + (size_t)(img0 + g) * C2_PIMG;
+        // both jobs' loads go out before the first select: one memory
+        // round trip per image (job c covers elements c*8 .. c*8+7)
+        short8 gv[2];
+        uint2 av[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          int c = tid + j * 256;
+          if (c < 49 * 8) {
+            gv[j] = *reinterpret_cast<const short8*>(gi + c * 8);
+            av[j] = *reinterpret_cast<const uint2*>(ai + c * 8);
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          int c = tid + j * 256;
+          if (c < 49 * 8) {
+            int chunk = c & 7, win = c >> 3;
+            int wy = win / 7, wx = win - wy * 7;
+#pragma unroll
+            for (int pos = 0; pos < 4; ++pos) {
+              int k = (2 * wy + (pos >> 1)) * 16 + 2 * wx + (pos & 1);
+              *reinterpret_cast<short8*>(D + k * 64 +
+                                         ((chunk ^ c2_dswz(k)) << 3)) =
+                  pool_bwd_select(gv[j], av[j], pos);
+            }
+          }
+        }
+      }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -274,20 +336,22 @@ int conv2_dw_group(int NB) {
   return G < 1 ? 1 : G;
 }
 
-template <int KHB, int NBUF>
+template <int KHB, int NBUF, bool POOLED = false>
 static void c2_launch(const unsigned short* x, const unsigned short* dact,
-                      float* dw, int NB, int G, int blocks, hipStream_t s) {
+                      float* dw, int NB, int G, int blocks, hipStream_t s,
+                      const uint8_t* am = nullptr) {
   constexpr int BYTES = NBUF * ((C2_MG * 2 + (13 + KHB) * 16) * 32 + 224 * 64) * 2;
   if (BYTES > 65536) {
     // above 64 KB the dynamic LDS size has to be granted once per kernel
     static const hipError_t granted = hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&conv2_dw_slab_kernel<KHB, NBUF>),
+        reinterpret_cast<const void*>(
+            &conv2_dw_slab_kernel<KHB, NBUF, POOLED>),
         hipFuncAttributeMaxDynamicSharedMemorySize, BYTES);
     if (granted != hipSuccess)
       throw std::runtime_error("conv2_dw_slab: LDS size not granted");
   }
-  hipLaunchKernelGGL((conv2_dw_slab_kernel<KHB, NBUF>), dim3(blocks),
-                     dim3(256), BYTES, s, x, dact, dw, NB, G);
+  hipLaunchKernelGGL((conv2_dw_slab_kernel<KHB, NBUF, POOLED>), dim3(blocks),
+                     dim3(256), BYTES, s, x, dact, dw, NB, G, am);
 }
 
 void launch_conv2_dw_slab(const unsigned short* x, const unsigned short* dact,
@@ -310,4 +374,16 @@ void launch_conv2_dw_slab(const unsigned short* x, const unsigned short* dact,
     c2_launch<1, 2>(x, dact, dw, NB, G, g8 * 5, s);
   else
     c2_launch<1, 1>(x, dact, dw, NB, G, g8 * 5, s);
+}
+
+// conv2 dW from the pooled gradient gp and the pool argmax bytes am (the
+// POOLED staging): same G tiers and XCD grouping as the dense launcher
+void launch_conv2_dw_slab_pooled(const unsigned short* x,
+                                 const unsigned short* gp, const uint8_t* am,
+                                 float* dw, int NB, hipStream_t s) {
+  if (NB <= 0) return;
+  int G = conv2_dw_group(NB);
+  int groups = (NB + G - 1) / G;
+  int g8 = (groups + 7) / 8 * 8;
+  c2_launch<1, 1, true>(x, gp, dw, NB, G, g8 * 5, s, am);
 }

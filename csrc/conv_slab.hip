@@ -222,12 +222,27 @@ void conv_fwd_slab_kernel(const u16* __restrict__ x,
 // ---------------------------------------------------------------------------
 // conv dX: dx[hi,wi,ci] = sum_{kh,kw,co} dact[hi-kh+2, wi-kw+2, co] *
 //          w[kh,kw,ci,co] — dact slab per image, W read from global per tile.
+//
+// POOLED: `dact` is the pooled gradient gp [NB][H/2][W/2][COUT] and `am` the
+// pool argmax bytes of the same shape; the dense pre-pool gradient exists
+// only in the slab.  A staging job is (2x2 window, 8-channel chunk): one 16 B
+// load of gp, one 8 B load of am, and one short8 LDS write per window
+// position pos = rr*2 + cc with element e = (am[e] == pos ? gp[e] : 0).  All
+// four positions are written, zeros included, so the slab is byte for byte
+// what the dense path stages and everything after the staging is shared.
+// am only feeds the compare, never an address: any byte outside 0..3 (7 =
+// dead window, or garbage) matches no position and the window stays zero.
+// Bounds: window (wy, wx) in 0..6 covers padded pixels (2wy+rr+2, 2wx+cc+2)
+// in 2..15, inside the HP x WP slab; the global reads are win*COUT + chunk*8
+// + 0..7 < (H/2)*(W/2)*COUT of this block's own image.
 // ---------------------------------------------------------------------------
-template <int H, int W, int CIN, int COUT, int DB = 2, int PAD = 8>
+template <int H, int W, int CIN, int COUT, int DB = 2, int PAD = 8,
+          bool POOLED = false>
 __global__ __launch_bounds__(NTHREADS)
 void conv_dx_slab_kernel(const u16* __restrict__ dact,
                          const u16* __restrict__ w,  // [25*CIN][COUT]
-                         u16* __restrict__ dx, int NB) {
+                         u16* __restrict__ dx, int NB,
+                         const uint8_t* __restrict__ am) {
   constexpr int HP = H + 4, WP = W + 4;
   constexpr int M = H * W;
   constexpr int BM = 224;
@@ -278,6 +293,50 @@ void conv_dx_slab_kernel(const u16* __restrict__ dact,
     glds16(src, &Bs[buf][wave * 8][0]);
   };
 
+  if (POOLED) {
+    constexpr int HO = H / 2, WO = W / 2;
+    const u16* gi = dact + (size_t)img * HO * WO * COUT;
+    const uint8_t* ai = am + (size_t)img * HO * WO * COUT;
+    // window jobs: every load goes out first (one memory round trip, under
+    // the halo fill); job c covers elements c*8 .. c*8+7 of the image
+    constexpr int NWJ = HO * WO * (COUT / 8);
+    constexpr int NJ = (NWJ + NTHREADS - 1) / NTHREADS;
+    short8 g[NJ];
+    uint2 a[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      int c = tid + j * NTHREADS;
+      if (c < NWJ) {
+        g[j] = *reinterpret_cast<const short8*>(gi + (size_t)c * 8);
+        a[j] = *reinterpret_cast<const uint2*>(ai + (size_t)c * 8);
+      }
+    }
+    // the 2-pixel halo ring; the interior is covered by the window jobs
+    for (int c = tid; c < HP * WP * (COUT / 8); c += NTHREADS) {
+      int co = (c % (COUT / 8)) * 8;
+      int pix = c / (COUT / 8);
+      int xx = pix % WP, yy = pix / WP;
+      int sy = yy - 2, sx = xx - 2;
+      if (!(sy >= 0 && sy < H && sx >= 0 && sx < W))
+        *reinterpret_cast<short8*>(&slab[(yy * WP + xx) * PST + co]) =
+            short8{0, 0, 0, 0, 0, 0, 0, 0};
+    }
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      int c = tid + j * NTHREADS;
+      if (c < NWJ) {
+        int co = (c % (COUT / 8)) * 8;
+        int win = c / (COUT / 8);
+        int wx = win % WO, wy = win / WO;
+#pragma unroll
+        for (int pos = 0; pos < 4; ++pos) {
+          int yy = 2 * wy + (pos >> 1) + 2, xx = 2 * wx + (pos & 1) + 2;
+          *reinterpret_cast<short8*>(&slab[(yy * WP + xx) * PST + co]) =
+              pool_bwd_select(g[j], a[j], pos);
+        }
+      }
+    }
+  } else {
   for (int c = tid; c < HP * WP * (COUT / 8); c += NTHREADS) {
     int co = (c % (COUT / 8)) * 8;
     int pix = c / (COUT / 8);
@@ -287,6 +346,7 @@ void conv_dx_slab_kernel(const u16* __restrict__ dact,
     if (sy >= 0 && sy < H && sx >= 0 && sx < W)
       v = *reinterpret_cast<const short8*>(di + ((size_t)sy * W + sx) * COUT + co);
     *reinterpret_cast<short8*>(&slab[(yy * WP + xx) * PST + co]) = v;
+  }
   }
 
   int arow_off[MI];
@@ -558,10 +618,12 @@ void launch_conv_dx_slab(const unsigned short* dact, const unsigned short* w,
     // scatter-staged kernel for A/B.
     if (getenv("DMNIST_DX_PAIR"))  // paired-K ablation (half the barriers)
       hipLaunchKernelGGL((conv_dx_slab_kernel<14, 14, 32, 64, 3>), dim3(NB),
-                         dim3(NTHREADS), 0, s, dact, w, dx, NB);
+                         dim3(NTHREADS), 0, s, dact, w, dx, NB,
+                         (const uint8_t*)nullptr);
     else if (NB < 2048)
       hipLaunchKernelGGL((conv_dx_slab_kernel<14, 14, 32, 64, 2>), dim3(NB),
-                         dim3(NTHREADS), 0, s, dact, w, dx, NB);
+                         dim3(NTHREADS), 0, s, dact, w, dx, NB,
+                         (const uint8_t*)nullptr);
     else if (getenv("DMNIST_DX_HIOCC"))
       hipLaunchKernelGGL((conv_dx_slab_hi_occ_kernel<14, 14, 32, 64>),
                          dim3(NB), dim3(NTHREADS), 0, s, dact, w, dx, NB);
@@ -570,11 +632,28 @@ void launch_conv_dx_slab(const unsigned short* dact, const unsigned short* w,
       // measured SLOWER than DB=1 at 8192 (357 vs 320 us solo) despite the
       // occupancy win; kept for A/B
       hipLaunchKernelGGL((conv_dx_slab_kernel<14, 14, 32, 64, 2, 4>),
-                         dim3(NB), dim3(NTHREADS), 0, s, dact, w, dx, NB);
+                         dim3(NB), dim3(NTHREADS), 0, s, dact, w, dx, NB,
+                         (const uint8_t*)nullptr);
     else
       hipLaunchKernelGGL((conv_dx_slab_kernel<14, 14, 32, 64, 1>), dim3(NB),
-                         dim3(NTHREADS), 0, s, dact, w, dx, NB);
+                         dim3(NTHREADS), 0, s, dact, w, dx, NB,
+                         (const uint8_t*)nullptr);
   }
+}
+
+// conv2 dX from the pooled gradient and the pool argmax bytes (POOLED
+// staging).  Same NB tiering as the dense launcher; force_db = 1 | 2 picks
+// either instantiation at any NB (0 = by NB).
+void launch_conv_dx_slab_pooled(const unsigned short* gp, const uint8_t* am,
+                                const unsigned short* w, unsigned short* dx,
+                                int NB, int force_db, hipStream_t s) {
+  int db = force_db ? force_db : (NB < 2048 ? 2 : 1);
+  if (db == 2)
+    hipLaunchKernelGGL((conv_dx_slab_kernel<14, 14, 32, 64, 2, 8, true>),
+                       dim3(NB), dim3(NTHREADS), 0, s, gp, w, dx, NB, am);
+  else
+    hipLaunchKernelGGL((conv_dx_slab_kernel<14, 14, 32, 64, 1, 8, true>),
+                       dim3(NB), dim3(NTHREADS), 0, s, gp, w, dx, NB, am);
 }
 
 // ---------------------------------------------------------------------------

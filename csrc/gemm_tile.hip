@@ -32,7 +32,7 @@ enum BMode {
   B_CONV_DX_W = 2, // Bmat[k=(khkw,co)][n=ci] = w[((khkw)*Cin+ci)*Cout + co]
 };
 enum Epi { EPI_NONE = 0, EPI_BIAS = 1, EPI_BIAS_RELU = 2, EPI_BIAS_RELU_DROP = 3,
-           EPI_POOL = 4, EPI_UNPOOL = 5, EPI_MASK_DB = 6 };
+           EPI_POOL = 4, EPI_UNPOOL = 5, EPI_MASK_DB = 6, EPI_POOLMASK_DB = 7 };
 // EPI_MASK_DB: dX epilogue that recovers the downstream relu+dropout mask
 // from the sign of the saved activation (actm) — v = a>0 ? v/p_keep : 0 —
 // and accumulates the bias grad db[n] (column sums).  Folds the standalone
@@ -46,6 +46,11 @@ enum Epi { EPI_NONE = 0, EPI_BIAS = 1, EPI_BIAS_RELU = 2, EPI_BIAS_RELU_DROP = 3
 // kernel into the producing dX GEMM (reference backward chain
 // mnist.py:115-127), removing one critical-path kernel + the pooled-grad
 // round trip.
+// EPI_POOLMASK_DB: EPI_UNPOOL without the scatter.  The value is masked by
+// the amax byte (g = amax < 4 ? acc : 0), summed into db[n % Cout] and stored
+// at C[m][n]: the output is the POOLED gradient gp [CB][CHo][CWo][Cout], zero
+// at dead windows, and the pre-pool dact is never written — its consumers
+// (conv_dx_pooled, conv_dw_pooled_into) rebuild it in LDS from (gp, amax).
 // OUT_F32_SLICES_FIX: OUT_F32_SLICES whose last block per tile also sums the
 // planes and writes the bf16 result (its own instantiation, so the plain
 // slices kernel carries none of it)
@@ -278,7 +283,8 @@ void gemm_tile_kernel(GemmParams p) {
   ushort_t (*Bs)[BN][LDK] =
       reinterpret_cast<ushort_t (*)[BN][LDK]>(smem + A_BYTES);
   // EPI_UNPOOL / EPI_MASK_DB: per-column bias-grad partials, flushed once
-  constexpr bool HAS_DB = (EPI == EPI_UNPOOL || EPI == EPI_MASK_DB);
+  constexpr bool HAS_DB = (EPI == EPI_UNPOOL || EPI == EPI_MASK_DB ||
+                           EPI == EPI_POOLMASK_DB);
   __shared__ float dbred[HAS_DB ? BN : 1];
   if (HAS_DB && threadIdx.x < BN) dbred[threadIdx.x] = 0.f;
 
@@ -290,8 +296,14 @@ void gemm_tile_kernel(GemmParams p) {
   // in registers when the k-loop ends.
   constexpr bool UNP = (EPI == EPI_UNPOOL) && (BN % 64 == 0) &&
                        (BM * BN / 16) % NTHREADS == 0 && SWZ == 0;
-  constexpr int NAM = UNP ? (BM * BN / 16) / NTHREADS : 1;
-  const bool use_lines = UNP && p.unpool_lines;
+  // EPI_POOLMASK_DB row-store path (host sets p.unpool_lines when N % 16 ==
+  // 0, ldc == N and both pointers are 16 B aligned): same amax prefetch,
+  // the masked bf16 tile is staged row-major in LDS and leaves as 16 B per
+  // lane, whole rows of the row-major output.
+  constexpr bool PML = (EPI == EPI_POOLMASK_DB) &&
+                       (BM * BN / 16) % NTHREADS == 0 && SWZ == 0;
+  constexpr int NAM = (UNP || PML) ? (BM * BN / 16) / NTHREADS : 1;
+  const bool use_lines = (UNP || PML) && p.unpool_lines;
   uint4 amreg[NAM];
   if (use_lines) {
     const int am_m0 = blockIdx.x * BM, am_n0 = blockIdx.y * BN;
@@ -451,8 +463,8 @@ void gemm_tile_kernel(GemmParams p) {
 epilogue:
   const int frow = (lane >> 4) * 4;  // C/D: row=(lane>>4)*4+reg, col=lane&15
   const int fcol = lane & 15;
-  float dbloc[(EPI == EPI_UNPOOL || EPI == EPI_MASK_DB) ? NI : 1];
-  if (EPI == EPI_UNPOOL || EPI == EPI_MASK_DB)
+  float dbloc[HAS_DB ? NI : 1];
+  if (HAS_DB)
 #pragma unroll
     for (int ni = 0; ni < NI; ++ni) dbloc[ni] = 0.f;
   if constexpr (UNP) {
@@ -532,6 +544,52 @@ epilogue:
       }
     }
   }
+  if constexpr (PML) {
+    if (use_lines) {
+      // Staging: bf16 tile [BM][BN + 8] (144 / 272 B rows: the four 16-lane
+      // groups of a wave write rows 4 apart, 16 banks apart), the amax tile
+      // [BM][BN + 16] bytes behind it (same 16-bank step for the byte reads).
+      constexpr int SST = (BN + 8) * 2, AST = BN + 16;
+      constexpr int STG = BM * SST;
+      static_assert(STG + BM * AST <= A_BYTES + B_BYTES, "staging fits LDS");
+      unsigned char* ams = smem + STG;
+      __syncthreads();  // every wave is done reading the operand images
+#pragma unroll
+      for (int i = 0; i < NAM; ++i) {
+        int idx = tid + i * NTHREADS;
+        int row = idx / (BN / 16), ch = idx % (BN / 16);
+        *reinterpret_cast<uint4*>(ams + row * AST + ch * 16) = amreg[i];
+      }
+      __syncthreads();
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < NI; ++ni) {
+          const int colt = wc * WN + ni * 16 + fcol;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int rowt = wr * WM + mi * 16 + frow + r;
+            // rows >= M and columns >= N were prefetched as 7 (dead)
+            int pos = ams[rowt * AST + colt];
+            float g = pos < 4 ? acc[mi][ni][r] : 0.f;
+            dbloc[ni] += g;
+            *reinterpret_cast<ushort_t*>(smem + rowt * SST + colt * 2) = f2bf(g);
+          }
+        }
+      __syncthreads();
+      ushort_t* gp = reinterpret_cast<ushort_t*>(p.C);
+      // BN / 8 consecutive lanes store one tile row (128 / 256 B)
+#pragma unroll
+      for (int i = 0; i < (BM * BN / 8) / NTHREADS; ++i) {
+        int idx = tid + i * NTHREADS;
+        int row = idx / (BN / 8), ch = idx % (BN / 8);
+        int gr = m0 + row, gc = n0 + ch * 8;
+        if (gr >= p.M || gc >= p.N) continue;  // N % 16 == 0: all in or out
+        *reinterpret_cast<uint4*>(gp + (size_t)gr * p.ldc + gc) =
+            *reinterpret_cast<const uint4*>(smem + row * SST + ch * 16);
+      }
+    }
+  }
   if (!use_lines) {
 #pragma unroll
   for (int mi = 0; mi < MI; ++mi) {
@@ -591,12 +649,18 @@ epilogue:
           int gr = m0 + wr * WM + mi * 16 + frow + r;
           if (gr >= p.M) continue;
           float v = acc[mi][ni][r];
+          if (EPI == EPI_POOLMASK_DB) {
+            int pos = p.amax[(size_t)gr * p.N + gc];  // 0..3 live, else dead
+            v = pos < 4 ? v : 0.f;
+            dbloc[ni] += v;
+          }
           if (EPI == EPI_MASK_DB) {
             float a = bf2f(p.actm[(size_t)gr * p.ldc + gc]);
             v = (a > 0.f) ? v * p.p_keep : 0.f;  // p_keep holds 1/keep here
             dbloc[ni] += v;
           }
-          if (EPI != EPI_NONE && EPI != EPI_MASK_DB) v += bias_v;
+          if (EPI != EPI_NONE && EPI != EPI_MASK_DB && EPI != EPI_POOLMASK_DB)
+            v += bias_v;
           if (EPI == EPI_BIAS_RELU || EPI == EPI_BIAS_RELU_DROP)
             v = v > 0.f ? v : 0.f;
           if (EPI == EPI_BIAS_RELU_DROP) {
@@ -713,7 +777,7 @@ epilogue:
       }
     }
   }
-  if (EPI == EPI_UNPOOL || EPI == EPI_MASK_DB) {
+  if (HAS_DB) {
     // bias-grad flush: lane partials -> LDS per-column -> one global
     // atomicAdd per block column (UNPOOL: channel = col % Cout)
 #pragma unroll
@@ -725,7 +789,8 @@ epilogue:
     if (p.db && (int)threadIdx.x < BN) {
       int gc = n0 + (int)threadIdx.x;
       float v = dbred[threadIdx.x];
-      int idx = (EPI == EPI_UNPOOL) ? gc % p.Cout : gc;
+      int idx = (EPI == EPI_UNPOOL || EPI == EPI_POOLMASK_DB) ? gc % p.Cout
+                                                               : gc;
       if (gc < p.N && v != 0.f) atomicAdd(&p.db[idx], v);
     }
   }
@@ -763,6 +828,9 @@ GEMM_ENTRY(gemm_dx_64, 64, 64, A_N, B_NMAJ, EPI_NONE, OUT_BF16, 1)
 // dX fused with maxpool-2x2 backward (fc1 dX -> dact2 directly + conv2 db)
 GEMM_ENTRY(gemm_dx_unpool_128, 128, 128, A_N, B_NMAJ, EPI_UNPOOL, OUT_BF16, 1)
 GEMM_ENTRY(gemm_dx_unpool_64, 64, 64, A_N, B_NMAJ, EPI_UNPOOL, OUT_BF16, 1)
+// dX masked by the pool2 argmax byte + conv2 db: the pooled gradient gp2
+GEMM_ENTRY(gemm_dx_poolmask_128, 128, 128, A_N, B_NMAJ, EPI_POOLMASK_DB, OUT_BF16, 1)
+GEMM_ENTRY(gemm_dx_poolmask_64, 64, 64, A_N, B_NMAJ, EPI_POOLMASK_DB, OUT_BF16, 1)
 // dX fused with the downstream relu/dropout mask + bias-grad column sums
 GEMM_ENTRY(gemm_dx_mask_128, 128, 128, A_N, B_NMAJ, EPI_MASK_DB, OUT_BF16, 1)
 GEMM_ENTRY(gemm_dx_mask_64, 64, 64, A_N, B_NMAJ, EPI_MASK_DB, OUT_BF16, 1)

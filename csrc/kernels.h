@@ -20,6 +20,7 @@ struct GemmParams {
   float* db;  // EPI_UNPOOL / EPI_MASK_DB: bias-grad accumulator
   const unsigned short* actm;  // EPI_MASK_DB: saved activation (mask source)
   int unpool_lines;   // EPI_UNPOOL: stage the tile in LDS, store 128 B lines
+                      // EPI_POOLMASK_DB: the same, whole 16 B row chunks
   unsigned* tickets;  // OUT_F32_SLICES_FIX: per-tile counters; the last slice
                       // of a tile sums the planes and writes bf16 y (p.Y)
   unsigned short* Y;  // OUT_F32_SLICES_FIX: final bf16 output [M][N]
@@ -37,6 +38,8 @@ void gemm_dx_128(const GemmParams&, hipStream_t);
 void gemm_dx_64(const GemmParams&, hipStream_t);
 void gemm_dx_unpool_128(const GemmParams&, hipStream_t);
 void gemm_dx_unpool_64(const GemmParams&, hipStream_t);
+void gemm_dx_poolmask_128(const GemmParams&, hipStream_t);
+void gemm_dx_poolmask_64(const GemmParams&, hipStream_t);
 void gemm_dx_mask_128(const GemmParams&, hipStream_t);
 void gemm_dx_mask_64(const GemmParams&, hipStream_t);
 void gemm_dw_128(const GemmParams&, hipStream_t);
@@ -164,6 +167,12 @@ void launch_conv_fwd_slab(const unsigned short* x, const unsigned short* w,
 void launch_conv_dx_slab(const unsigned short* dact, const unsigned short* w,
                          unsigned short* dx, int NB, int H, int W, int Cin,
                          int Cout, hipStream_t);
+// the same from the pooled gradient gp [NB][7][7][64] + pool argmax bytes:
+// the dense dact is rebuilt in the LDS slab only.  force_db = 1 | 2 picks the
+// large- / small-batch instantiation at any NB, 0 = by NB
+void launch_conv_dx_slab_pooled(const unsigned short* gp, const uint8_t* am,
+                                const unsigned short* w, unsigned short* dx,
+                                int NB, int force_db, hipStream_t);
 void launch_conv_dw_slab(const unsigned short* x, const unsigned short* dact,
                          float* dw, int NB, int H, int W, int Cin, int Cout,
                          hipStream_t);
@@ -195,6 +204,10 @@ bool conv2_dw_slab_enabled();
 int conv2_dw_group(int NB);  // images per block the launcher picks
 void launch_conv2_dw_slab(const unsigned short* x, const unsigned short* dact,
                           float* dw, int NB, hipStream_t);
+// the same from the pooled gradient gp [NB][7][7][64] + pool argmax bytes
+void launch_conv2_dw_slab_pooled(const unsigned short* x,
+                                 const unsigned short* gp, const uint8_t* am,
+                                 float* dw, int NB, hipStream_t);
 // gemm_tile.hip — split-K fwd slice entries + their summing epilogue
 void gemm_fwd_slices_64(const GemmParams&, hipStream_t);
 void gemm_fwd_slices_64_bt(const GemmParams&, hipStream_t);

@@ -3,14 +3,19 @@
 Replaces autograd's serial backward with an explicit schedule; used inside
 the hipGraph capture (graphstep.py).
 
-Backward dataflow (round 2, pool backward fused away):
+Backward dataflow (both pool backwards fused into their consumers: neither
+pre-pool gradient, dact1 or dact2, is ever written to memory):
 
   softmax(+db2) -> dl --> dW2
      dl --> dx2+mask+db1 = dyeff1 --> dW1
-              dyeff1 --> dX+unpool = dact2 (+db_conv2) --> conv2 dW
-                          dact2 --> conv_dx = dxc --> conv1 dW+db (pooled)
+              dyeff1 --> dX+poolmask = gp2 [B,7,7,64] (+db_conv2)
+                (gp2, am2) --> conv2 dW   (dact2 rebuilt in the LDS slab)
+                (gp2, am2) --> conv2 dX = dxc --> conv1 dW+db (pooled)
 All dW/db land directly in the flat fp32 all-reduce bucket (zeroed by the
 SGD tail of the previous step).
+
+DMNIST_POOL2_FUSED=0 selects the earlier three calls, which materialise the
+dense dact2 [B,14,14,64] (dX+unpool -> conv_dw_into / conv_dx), for A/B.
 
 Round-1 ran the dW chain on a SIDE stream overlapping the dX chain;
 round-2 same-box A/B showed the single-stream schedule is ~7% faster
@@ -59,6 +64,9 @@ class FusedLeNetStep:
         else:
             self.overlap_level = 0 if t.flags.batch_size < 4096 else 2
         self.single_stream = self.overlap_level == 0
+        # pool2 backward inside the conv2 dX / dW staging (gp2 + am2, no
+        # dense dact2); DMNIST_POOL2_FUSED=0 keeps the dX+unpool route
+        self.pool2_fused = _os.environ.get("DMNIST_POOL2_FUSED", "1") != "0"
         # side stream resolved PER CALL: in single-stream mode it must be
         # whatever stream the body is running on RIGHT NOW (warmup and
         # graph capture run on their own streams — freezing the init-time
@@ -132,17 +140,16 @@ class FusedLeNetStep:
                 # ordered by wait_stream) is final here
                 self.t.engine.wire_allreduce(self.fc_slice,
                                              start=self.fc_offset)
-        # fc1 dX fused with pool2 backward: dact2 + conv2 db come straight
-        # out of the GEMM epilogue (no pool_scatter kernel on the chain;
-        # liveness rides in the amax byte, no y2 re-read)
-        dact2 = ext.linear_dx_unpool(dyeff1, sh["fc1_w"], am2,
-                                     gv("conv2_b"), 7, 7, 64)
+        # fc1 dX with the pool2 mask + conv2 db in the GEMM epilogue
+        # (liveness rides in the amax byte, no y2 re-read); pool2 backward
+        # itself happens in the conv2 dW / dX slab staging
+        g2 = self._fc1_dx(dyeff1, am2)
         sW = s1 if self.overlap_level >= 2 else s0  # conv2 dW placement
         if sW is not s0:
             self._fork(sW, s0)
         with torch.cuda.stream(sW):
-            ext.conv_dw_into(y1, dact2, gv("conv2_w"))
-        dxc = ext.conv_dx(dact2, sh["conv2_w"], 32)
+            self._conv2_dw(y1, g2, am2)
+        dxc = self._conv2_dx(g2, am2)
 
         # conv1 dW+db consume the POOLED gradient (pool1 backward fused in
         # the consumer; the 4x-size dact1 is never materialized)
@@ -152,8 +159,29 @@ class FusedLeNetStep:
         if self.overlap_allreduce:
             self.t.engine.wire_allreduce(self.conv_slice, start=0)
         # keep the side-stream consumers alive until the join (capture-safe)
-        self._keep = (a1, h2, dyeff1, dl, y1, dact2)
+        self._keep = (a1, h2, dyeff1, dl, y1, g2, am2)
         return loss, acc
+
+    # pool2 backward: g2 is the pooled gradient gp2 [B,7,7,64] (default) or,
+    # with DMNIST_POOL2_FUSED=0, the dense dact2 [B,14,14,64]
+    def _fc1_dx(self, dyeff1, am2):
+        m = self.t.model
+        f = (self.ext.linear_dx_pooled if self.pool2_fused
+             else self.ext.linear_dx_unpool)
+        return f(dyeff1, m.shadows["fc1_w"], am2, m.conv2_b.grad, 7, 7, 64)
+
+    def _conv2_dw(self, y1, g2, am2):
+        dw = self.t.model.conv2_w.grad
+        if self.pool2_fused:
+            self.ext.conv_dw_pooled_into(y1, g2, am2, dw)
+        else:
+            self.ext.conv_dw_into(y1, g2, dw)
+
+    def _conv2_dx(self, g2, am2):
+        w = self.t.model.shadows["conv2_w"]
+        if self.pool2_fused:
+            return self.ext.conv_dx_pooled(g2, am2, w, 32)
+        return self.ext.conv_dx(g2, w, 32)
 
     # ------------------------------------------------------------------
     # Two-stage form of the SAME schedule, for the two-graph split capture
@@ -197,12 +225,11 @@ class FusedLeNetStep:
         self._fork(s1, s0)
         with torch.cuda.stream(s1):
             ext.linear_dw_into(h2, dyeff1, gv("fc1_w"))
-        # fused dX+pool2-backward: conv2_b lands here (conv slice — reduced
+        # fc1 dX + pool2 mask: conv2_b lands here (conv slice — reduced
         # after graph B, so computing it early is safe)
-        dact2 = ext.linear_dx_unpool(dyeff1, sh["fc1_w"], am2,
-                                     gv("conv2_b"), 7, 7, 64)
+        g2 = self._fc1_dx(dyeff1, am2)
         s0.wait_stream(s1)  # graph A boundary: fc grads complete
-        self._stash = (x, y1, am1, dact2)
+        self._stash = (x, y1, am1, g2, am2)
         self._keep = (a1, h2, dyeff1, dl)
         return loss, acc
 
@@ -213,15 +240,15 @@ class FusedLeNetStep:
         def gv(name):
             return getattr(m, name).grad
 
-        x, y1, am1, dact2 = self._stash
+        x, y1, am1, g2, am2 = self._stash
         s0 = torch.cuda.current_stream()
         s1 = s0 if self.single_stream else self.side
         sW = s1 if self.overlap_level >= 2 else s0  # conv2 dW placement
         if sW is not s0:
             self._fork(sW, s0)
         with torch.cuda.stream(sW):
-            ext.conv_dw_into(y1, dact2, gv("conv2_w"))
-        dxc = ext.conv_dx(dact2, m.shadows["conv2_w"], 32)
+            self._conv2_dw(y1, g2, am2)
+        dxc = self._conv2_dx(g2, am2)
         ext.conv1_dw_pooled(x, dxc, am1, gv("conv1_w"), gv("conv1_b"))
         self._fork(s0, s1)
-        self._keep2 = (dact2,)
+        self._keep2 = (g2, am2)

@@ -4,7 +4,8 @@ one process (every switch is read per call):
   dW      DMNIST_DW_PLAN = tbm,bn,splitk over {64,128} x {64,128} x {1,2,4},
           against the pre-plan choice (DMNIST_DW_PLAN=0) and the launcher's
           default plan;
-  dX      DMNIST_UNPOOL_LINES x DMNIST_UNPOOL_TILE;
+  dX      DMNIST_UNPOOL_LINES x DMNIST_UNPOOL_TILE, and the pooled-gradient
+          producer linear_dx_pooled at both tiles;
   forward DMNIST_FC_FIXUP (split-K route only).
 Solo launches timed with device events, median of 60, us."""
 import os, sys
@@ -64,6 +65,14 @@ for B in [int(a) for a in sys.argv[1:]] or [1024, 8192]:
         a = timed(run, DMNIST_UNPOOL_TILE=tile, DMNIST_UNPOOL_LINES="0")
         b = timed(run, DMNIST_UNPOOL_TILE=tile)
         print(f"| tile {tile} | {a:.1f} | {b:.1f} |", flush=True)
+
+    print("| dX+poolmask (gp2, no dact2) | us |")
+    print("|---|---|")
+    for tile in (64, 128):
+        us = timeit(lambda: ext.linear_dx_pooled(dyeff1, w, am, dbc, 7, 7,
+                                                 64, tile=tile), iters=60)
+        print(f"| tile {tile} | {us:.1f} |", flush=True)
+    print(f"launcher default: tile {ext.linear_dx_pooled_tile(B, 3136)}")
 
     run = lambda: ext.linear_act_fwd(h2, w, bias, True, 0.5, 1, 2, wT=wT)
     a = timed(run, DMNIST_FC_FIXUP="0")

@@ -71,6 +71,7 @@ def bench_batch(ext, B):
     dbc2 = torch.zeros(64, device=dev)
     dact2 = ext.pool_scatter(dx1, y2, am2, dbc2, 14, 14)
     dwc2 = torch.zeros(5, 5, 32, 64, device=dev)
+    gp2 = ext.linear_dx_pooled(dyeff1, f1, am2, dbc2, 7, 7, 64)
     dxc = ext.conv_dx(dact2, w2, 32)
     dbc1 = torch.zeros(32, device=dev)
     dact1 = ext.pool_scatter(dxc, y1, am1, dbc1, 28, 28)
@@ -95,8 +96,11 @@ def bench_batch(ext, B):
         ("fc1 dX", lambda: ext.linear_dx(dyeff1, f1)),
         ("pool2 bwd scatter", lambda: ext.pool_scatter(dx1, y2, am2, dbc2, 14, 14)),
         ("fc1 dX+unpool fused", lambda: ext.linear_dx_unpool(dyeff1, f1, am2, dbc2, 7, 7, 64)),
+        ("fc1 dX+poolmask (pooled gradient, no dact2)", lambda: ext.linear_dx_pooled(dyeff1, f1, am2, dbc2, 7, 7, 64)),
         ("conv2 dW (slab/gemm tiered)", lambda: ext.conv_dw_into(y1, dact2, dwc2)),
+        ("conv2 dW from (gp2, am2) (slab, pool bwd in staging)", lambda: ext.conv_dw_pooled_into(y1, gp2, am2, dwc2.view(-1))),
         ("conv2 dX (image slab)", lambda: ext.conv_dx(dact2, w2, 32)),
+        ("conv2 dX from (gp2, am2) (image slab, pool bwd in staging)", lambda: ext.conv_dx_pooled(gp2, am2, w2, 32)),
         ("pool1 bwd scatter", lambda: ext.pool_scatter(dxc, y1, am1, dbc1, 28, 28)),
         ("conv1 dW from dact (direct dot2 VALU)", lambda: ext.conv_dw_into(x1, dact1, dwc1)),
         ("conv1 dW+db pooled fused (MFMA; DMNIST_CONV1_VALU=1: dot2 VALU)", lambda: ext.conv1_dw_pooled(x1, dxc, am1, dwc1.view(-1), dbc1)),
