@@ -843,10 +843,25 @@ std::vector<torch::Tensor> softmax_xent_fwd(torch::Tensor logits,
   return {loss, correct, dl};
 }
 
+// optional moving-average buffer of the SGD pass: nullptr = off
+static float* ema_ptr(const c10::optional<torch::Tensor>& ema,
+                      const torch::Tensor& master, double ema_decay) {
+  if (!ema.has_value() || !ema->defined()) return nullptr;
+  CHECK_CUDA((*ema)); CHECK_F32((*ema)); CHECK_CONTIG((*ema));
+  TORCH_CHECK(ema->numel() >= master.numel(),
+              "sgd_step: ema is shorter than master");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(ema->data_ptr()) % 16 == 0,
+              "sgd_step: ema must be 16-byte aligned");
+  TORCH_CHECK(ema_decay >= 0.0 && ema_decay < 1.0,
+              "sgd_step: ema_decay must lie in [0, 1)");
+  return ema->data_ptr<float>();
+}
+
 void sgd_step(torch::Tensor master, torch::Tensor grad, torch::Tensor shadow,
               bool has_shadow, double lr, double scale, double dc_keep,
               int64_t seed, int64_t offset,
-              c10::optional<torch::Tensor> momentum, double mu) {
+              c10::optional<torch::Tensor> momentum, double mu,
+              c10::optional<torch::Tensor> ema, double ema_decay) {
   CHECK_CUDA(master); CHECK_F32(master); CHECK_CONTIG(master);
   CHECK_F32(grad); CHECK_CONTIG(grad);
   float* mom = nullptr;
@@ -854,11 +869,13 @@ void sgd_step(torch::Tensor master, torch::Tensor grad, torch::Tensor shadow,
     CHECK_F32((*momentum)); CHECK_CONTIG((*momentum));
     mom = momentum->data_ptr<float>();
   }
+  float* emap = ema_ptr(ema, master, ema_decay);
   launch_sgd_step(master.data_ptr<float>(), grad.data_ptr<float>(),
                   has_shadow ? bf16_mut(shadow) : nullptr,
                   has_shadow ? 1 : 0, master.numel(),
                   (float)(lr * scale), (float)dc_keep, (uint64_t)seed,
-                  (uint64_t)offset, mom, (float)mu, cur_stream());
+                  (uint64_t)offset, mom, (float)mu, emap, (float)ema_decay,
+                  cur_stream());
 }
 
 void sgd_step_dev(torch::Tensor master, torch::Tensor grad,
@@ -866,7 +883,8 @@ void sgd_step_dev(torch::Tensor master, torch::Tensor grad,
                   torch::Tensor lr_scale_dev, double dc_keep, int64_t seed,
                   torch::Tensor offset_dev,
                   c10::optional<torch::Tensor> momentum, double mu,
-                  bool zero_grad) {
+                  bool zero_grad, c10::optional<torch::Tensor> ema,
+                  double ema_decay) {
   CHECK_CUDA(master); CHECK_F32(master); CHECK_CONTIG(master);
   CHECK_F32(grad); CHECK_CONTIG(grad);
   CHECK_F32(lr_scale_dev);
@@ -880,7 +898,37 @@ void sgd_step_dev(torch::Tensor master, torch::Tensor grad,
                       has_shadow ? 1 : 0, master.numel(),
                       lr_scale_dev.data_ptr<float>(), (float)dc_keep,
                       (uint64_t)seed, offset_dev.data_ptr<long>(),
-                      mom, (float)mu, zero_grad ? 1 : 0, cur_stream());
+                      mom, (float)mu, zero_grad ? 1 : 0,
+                      ema_ptr(ema, master, ema_decay), (float)ema_decay,
+                      cur_stream());
+}
+
+void ema_publish(torch::Tensor ema, torch::Tensor shadow,
+                 std::vector<int64_t> offsets, std::vector<int64_t> rows,
+                 std::vector<int64_t> cols, std::vector<torch::Tensor> dsts) {
+  // flat fp32 parameters -> flat bf16 shadow + the transposed bf16 copies
+  // dsts[i] [C][R] of the row-major [R][C] slice at offsets[i]; one launch
+  CHECK_CUDA(ema); CHECK_F32(ema); CHECK_CONTIG(ema);
+  CHECK_CUDA(shadow); CHECK_BF16(shadow); CHECK_CONTIG(shadow);
+  TORCH_CHECK(shadow.numel() == ema.numel(), "ema_publish: shadow size");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(ema.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(shadow.data_ptr()) % 8 == 0,
+              "ema_publish: ema must be 16-byte and shadow 8-byte aligned");
+  size_t nt = dsts.size();
+  TORCH_CHECK(nt <= 4 && offsets.size() == nt && rows.size() == nt &&
+              cols.size() == nt, "ema_publish: up to 4 transposed tensors");
+  EmaTransposeDesc d[4];
+  for (size_t i = 0; i < nt; ++i) {
+    CHECK_CUDA(dsts[i]); CHECK_BF16(dsts[i]); CHECK_CONTIG(dsts[i]);
+    TORCH_CHECK(rows[i] > 0 && cols[i] > 0 && offsets[i] >= 0 &&
+                rows[i] * cols[i] <= ema.numel() - offsets[i],
+                "ema_publish: slice ", i, " lies outside the buffer");
+    TORCH_CHECK(dsts[i].numel() == rows[i] * cols[i],
+                "ema_publish: transposed copy ", i, " has the wrong size");
+    d[i] = {(long)offsets[i], bf16_mut(dsts[i]), (int)rows[i], (int)cols[i]};
+  }
+  launch_ema_publish(ema.data_ptr<float>(), bf16_mut(shadow), ema.numel(), d,
+                     (int)nt, cur_stream());
 }
 
 void transpose_bf16_batch(std::vector<torch::Tensor> srcs,
@@ -1211,7 +1259,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("master"), py::arg("grad"), py::arg("shadow"),
         py::arg("has_shadow"), py::arg("lr"), py::arg("scale"),
         py::arg("dc_keep"), py::arg("seed"), py::arg("offset"),
-        py::arg("momentum") = c10::nullopt, py::arg("mu") = 0.0);
+        py::arg("momentum") = c10::nullopt, py::arg("mu") = 0.0,
+        py::arg("ema") = c10::nullopt, py::arg("ema_decay") = 0.0);
+  m.def("ema_publish", &ema_publish,
+        "flat fp32 parameters -> flat bf16 shadow + transposed bf16 copies "
+        "of the [rows][cols] slices at `offsets`, one launch",
+        py::arg("ema"), py::arg("shadow"), py::arg("offsets"),
+        py::arg("rows"), py::arg("cols"), py::arg("dsts"));
   m.def("sgd_step_dev", &sgd_step_dev,
         "SGD apply with device-side lr/offset (hipGraph-capturable); "
         "zero_grad clears the bucket in the same pass",
@@ -1219,7 +1273,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("has_shadow"), py::arg("lr_scale_dev"), py::arg("dc_keep"),
         py::arg("seed"), py::arg("offset_dev"),
         py::arg("momentum") = c10::nullopt, py::arg("mu") = 0.0,
-        py::arg("zero_grad") = false);
+        py::arg("zero_grad") = false,
+        py::arg("ema") = c10::nullopt, py::arg("ema_decay") = 0.0);
   m.def("step_advance", &step_advance,
         "device-side staircase LR + step increment (inside the graph)");
   m.def("grad_mask", &grad_mask,

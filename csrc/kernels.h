@@ -74,14 +74,35 @@ void launch_softmax_xent(const unsigned short* logits, const long* labels,
 void launch_sgd_step(float* master, float* grad, unsigned short* shadow,
                      int has_shadow, long n, float lr_scale, float dc_keep,
                      uint64_t seed, uint64_t offset, float* momentum, float mu,
-                     hipStream_t);
+                     float* ema, float ema_decay, hipStream_t);
 // graph-capturable variants: lr_scale / RNG offset read from device memory
 void launch_sgd_step_dev(float* master, float* grad,
                          unsigned short* shadow, int has_shadow, long n,
                          const float* lr_scale_dev, float dc_keep,
                          uint64_t seed, const long* offset_dev,
                          float* momentum, float mu, int zero_grad,
-                         hipStream_t);
+                         float* ema, float ema_decay, hipStream_t);
+// ema != nullptr (both launchers): the same pass also moves the fp32 moving
+// average towards the new master, e -= (1 - d_k)*(e - w) with
+// d_k = min(ema_decay, (1 + k)/(10 + k)), k = offset + 1 (a second
+// instantiation; ema == nullptr launches the unchanged sgd_step_kernel).
+// ema_publish: flat fp32 `src` [n] -> bf16 `shadow` [n] plus the transposed
+// bf16 copies dst[C][R] of up to 4 row-major [R][C] slices of src, one launch.
+struct EmaTransposeDesc {
+  long offset;  // element offset of the [R][C] slice in src
+  unsigned short* dst;
+  int R, C;
+};
+struct EmaPublishArgs {
+  const float* src;
+  unsigned short* shadow;
+  long n;
+  EmaTransposeDesc d[4];
+  int tile0[4];
+  int nt, flat_blocks;
+};
+void launch_ema_publish(const float* src, unsigned short* shadow, long n,
+                        const EmaTransposeDesc* descs, int nt, hipStream_t);
 void launch_conv1_dw_pooled(const unsigned short* x, const unsigned short* dyp,
                             const uint8_t* am, float* dw, float* db, int NB,
                             int H, int W, int Cout, hipStream_t s);

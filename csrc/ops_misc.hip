@@ -288,21 +288,33 @@ void softmax_xent_t_kernel(const ushort_t* logits, const long* labels,
 // shadow = bf16(master).  Drop-connect = reference distributed_train.py:414
 // (mask, NO rescale).  Vectorized float4 path + scalar tail.
 // ---------------------------------------------------------------------------
-extern "C" __global__ __launch_bounds__(256)
-void sgd_step_kernel(float* master, float* grad, ushort_t* shadow,
-                     int has_shadow, long n, float lr_scale, float dc_keep,
-                     uint64_t seed, uint64_t offset,
-                     const float* lr_scale_dev, const long* offset_dev,
-                     float* momentum, float mu, int zero_grad) {
+// EMA (compile-time variant, TensorFlow ExponentialMovingAverage with
+// num_updates): update k = offset + 1 moves the average `ema` towards the
+// master value just written, e -= (1 - d_k)*(e - w), d_k = min(ema_decay,
+// (1 + k)/(10 + k)) — one more fp32 read-modify-write stream in the same
+// pass, fed from the master already in registers.  EMA = false compiles to
+// exactly the pass without it.
+template <bool EMA>
+__device__ __forceinline__
+void sgd_step_body(float* master, float* grad, ushort_t* shadow,
+                   int has_shadow, long n, float lr_scale, float dc_keep,
+                   uint64_t seed, uint64_t offset,
+                   float* momentum, float mu, int zero_grad,
+                   float* ema, float ema_decay, long i, long stride) {
+  // lr_scale / offset: already resolved from their device copies;
+  // i / stride: the caller's grid-stride start and step, in float4 groups
+  // (blockDim read in here costs a run-time workgroup-size lookup that the
+  // same expression in the __global__ function does not)
   // zero_grad: clear the flat gradient bucket in the SAME pass that
   // consumes it (the captured graph then needs no per-step fill kernel;
   // all dW/db writers accumulate with atomics into a zeroed bucket)
   // momentum (optional): v = mu*v + g; w -= lr*v  (v=nullptr => plain SGD,
   // the reference's GradientDescentOptimizer semantics)
-  if (lr_scale_dev) lr_scale = *lr_scale_dev;
-  if (offset_dev) offset = (uint64_t)*offset_dev;
-  long i = (long)(blockIdx.x) * blockDim.x + threadIdx.x;
-  long stride = (long)gridDim.x * blockDim.x;
+  float ema_w = 0.f;  // 1 - d_k
+  if (EMA) {
+    float k = (float)(offset + 1);
+    ema_w = 1.f - fminf(ema_decay, (1.f + k) / (10.f + k));
+  }
   for (; i * 4 < n; i += stride) {
     long base = i * 4;
     if (base + 3 < n) {
@@ -326,6 +338,12 @@ void sgd_step_kernel(float* master, float* grad, ushort_t* shadow,
       m.x -= lr_scale * g.x; m.y -= lr_scale * g.y;
       m.z -= lr_scale * g.z; m.w -= lr_scale * g.w;
       *reinterpret_cast<float4*>(master + base) = m;
+      if (EMA) {
+        float4 e = *reinterpret_cast<const float4*>(ema + base);
+        e.x -= ema_w * (e.x - m.x); e.y -= ema_w * (e.y - m.y);
+        e.z -= ema_w * (e.z - m.z); e.w -= ema_w * (e.w - m.w);
+        *reinterpret_cast<float4*>(ema + base) = e;
+      }
       if (zero_grad)
         *reinterpret_cast<float4*>(grad + base) = float4{0.f, 0.f, 0.f, 0.f};
       if (has_shadow) {
@@ -346,11 +364,44 @@ void sgd_step_kernel(float* master, float* grad, ushort_t* shadow,
         }
         float m = master[j] - lr_scale * g;
         master[j] = m;
+        if (EMA) {
+          float e = ema[j];
+          ema[j] = e - ema_w * (e - m);
+        }
         if (zero_grad) grad[j] = 0.f;
         if (has_shadow) shadow[j] = f2bf(m);
       }
     }
   }
+}
+
+extern "C" __global__ __launch_bounds__(256)
+void sgd_step_kernel(float* master, float* grad, ushort_t* shadow,
+                     int has_shadow, long n, float lr_scale, float dc_keep,
+                     uint64_t seed, uint64_t offset,
+                     const float* lr_scale_dev, const long* offset_dev,
+                     float* momentum, float mu, int zero_grad) {
+  if (lr_scale_dev) lr_scale = *lr_scale_dev;
+  if (offset_dev) offset = (uint64_t)*offset_dev;
+  sgd_step_body<false>(master, grad, shadow, has_shadow, n, lr_scale, dc_keep,
+                       seed, offset, momentum, mu, zero_grad, nullptr, 0.f,
+                       (long)(blockIdx.x) * blockDim.x + threadIdx.x,
+                       (long)gridDim.x * blockDim.x);
+}
+
+extern "C" __global__ __launch_bounds__(256)
+void sgd_step_kernel_ema(float* master, float* grad, ushort_t* shadow,
+                         int has_shadow, long n, float lr_scale, float dc_keep,
+                         uint64_t seed, uint64_t offset,
+                         const float* lr_scale_dev, const long* offset_dev,
+                         float* momentum, float mu, int zero_grad,
+                         float* ema, float ema_decay) {
+  if (lr_scale_dev) lr_scale = *lr_scale_dev;
+  if (offset_dev) offset = (uint64_t)*offset_dev;
+  sgd_step_body<true>(master, grad, shadow, has_shadow, n, lr_scale, dc_keep,
+                      seed, offset, momentum, mu, zero_grad, ema, ema_decay,
+                      (long)(blockIdx.x) * blockDim.x + threadIdx.x,
+                      (long)gridDim.x * blockDim.x);
 }
 
 // step/LR advance: device-side staircase LR so a captured graph needs no
@@ -476,14 +527,20 @@ void launch_softmax_xent(const unsigned short* logits, const long* labels,
 void launch_sgd_step(float* master, float* grad, unsigned short* shadow,
                      int has_shadow, long n, float lr_scale, float dc_keep,
                      uint64_t seed, uint64_t offset, float* momentum, float mu,
-                     hipStream_t s) {
+                     float* ema, float ema_decay, hipStream_t s) {
   long groups = (n + 3) / 4;
   int blocks = (int)min((long)2048, (groups + 255) / 256);
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(sgd_step_kernel, dim3(blocks), dim3(256), 0, s, master,
-                     grad, shadow, has_shadow, n, lr_scale, dc_keep, seed,
-                     offset, (const float*)nullptr, (const long*)nullptr,
-                     momentum, mu, 0);
+  if (ema)
+    hipLaunchKernelGGL(sgd_step_kernel_ema, dim3(blocks), dim3(256), 0, s,
+                       master, grad, shadow, has_shadow, n, lr_scale, dc_keep,
+                       seed, offset, (const float*)nullptr,
+                       (const long*)nullptr, momentum, mu, 0, ema, ema_decay);
+  else
+    hipLaunchKernelGGL(sgd_step_kernel, dim3(blocks), dim3(256), 0, s, master,
+                       grad, shadow, has_shadow, n, lr_scale, dc_keep, seed,
+                       offset, (const float*)nullptr, (const long*)nullptr,
+                       momentum, mu, 0);
 }
 
 void launch_sgd_step_dev(float* master, float* grad,
@@ -491,13 +548,90 @@ void launch_sgd_step_dev(float* master, float* grad,
                          const float* lr_scale_dev, float dc_keep,
                          uint64_t seed, const long* offset_dev,
                          float* momentum, float mu, int zero_grad,
-                         hipStream_t s) {
+                         float* ema, float ema_decay, hipStream_t s) {
   long groups = (n + 3) / 4;
   int blocks = (int)min((long)2048, (groups + 255) / 256);
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(sgd_step_kernel, dim3(blocks), dim3(256), 0, s, master,
-                     grad, shadow, has_shadow, n, 0.f, dc_keep, seed, 0,
-                     lr_scale_dev, offset_dev, momentum, mu, zero_grad);
+  if (ema)
+    hipLaunchKernelGGL(sgd_step_kernel_ema, dim3(blocks), dim3(256), 0, s,
+                       master, grad, shadow, has_shadow, n, 0.f, dc_keep, seed,
+                       0, lr_scale_dev, offset_dev, momentum, mu, zero_grad,
+                       ema, ema_decay);
+  else
+    hipLaunchKernelGGL(sgd_step_kernel, dim3(blocks), dim3(256), 0, s, master,
+                       grad, shadow, has_shadow, n, 0.f, dc_keep, seed, 0,
+                       lr_scale_dev, offset_dev, momentum, mu, zero_grad);
+}
+
+// ---------------------------------------------------------------------------
+// ema_publish: turn a flat fp32 parameter buffer (the EMA) into what the
+// forward kernels read, in ONE launch: blocks [0, flat_blocks) write the flat
+// bf16 shadow (sgd_step_kernel's f2bf rounding), the rest write the
+// pre-transposed bf16 copies through 32x32 LDS tiles (the layout of
+// transpose_bf16_batch_kernel, reading fp32 and converting on the way).
+// Runs once per evaluation, never per step.
+// ---------------------------------------------------------------------------
+extern "C" __global__ __launch_bounds__(256)
+void ema_publish_kernel(EmaPublishArgs a) {
+  __shared__ ushort_t tile[32][33];
+  if ((int)blockIdx.x < a.flat_blocks) {
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    long stride = (long)a.flat_blocks * blockDim.x;
+    for (; i * 4 < a.n; i += stride) {
+      long base = i * 4;
+      if (base + 3 < a.n) {
+        float4 e = *reinterpret_cast<const float4*>(a.src + base);
+        ushort4 o;
+        o.x = f2bf(e.x); o.y = f2bf(e.y); o.z = f2bf(e.z); o.w = f2bf(e.w);
+        *reinterpret_cast<ushort4*>(a.shadow + base) = o;
+      } else {
+        for (long j = base; j < a.n; ++j) a.shadow[j] = f2bf(a.src[j]);
+      }
+    }
+    return;
+  }
+  int t = (int)blockIdx.x - a.flat_blocks;
+  int which = 0;
+  while (which + 1 < a.nt && t >= a.tile0[which + 1]) ++which;
+  int local = t - a.tile0[which];
+  const EmaTransposeDesc d = a.d[which];
+  const float* src = a.src + d.offset;
+  int ctiles = (d.C + 31) / 32;
+  int tr0 = (local / ctiles) * 32;
+  int tc0 = (local % ctiles) * 32;
+  int lx = threadIdx.x & 31, ly = threadIdx.x >> 5;
+#pragma unroll
+  for (int rr = 0; rr < 4; ++rr) {
+    int r = tr0 + ly + rr * 8, c = tc0 + lx;
+    tile[ly + rr * 8][lx] = (r < d.R && c < d.C)
+        ? f2bf(src[(size_t)r * d.C + c]) : (ushort_t)0;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int rr = 0; rr < 4; ++rr) {
+    int c = tc0 + ly + rr * 8, r = tr0 + lx;
+    if (c < d.C && r < d.R) d.dst[(size_t)c * d.R + r] = tile[lx][ly + rr * 8];
+  }
+}
+
+void launch_ema_publish(const float* src, unsigned short* shadow, long n,
+                        const EmaTransposeDesc* descs, int nt, hipStream_t s) {
+  EmaPublishArgs a{};
+  a.src = src;
+  a.shadow = shadow;
+  a.n = n;
+  long groups = (n + 3) / 4;
+  a.flat_blocks = (int)min((long)2048, (groups + 255) / 256);
+  if (a.flat_blocks < 1) a.flat_blocks = 1;
+  int total = 0;
+  for (int i = 0; i < nt && i < 4; ++i) {
+    a.d[i] = descs[i];
+    a.tile0[i] = total;
+    total += ((descs[i].C + 31) / 32) * ((descs[i].R + 31) / 32);
+  }
+  a.nt = nt < 4 ? nt : 4;
+  hipLaunchKernelGGL(ema_publish_kernel, dim3(a.flat_blocks + total),
+                     dim3(256), 0, s, a);
 }
 
 // ---------------------------------------------------------------------------

@@ -48,6 +48,20 @@ def resolve_eval_device(flags):
     return device, dtype
 
 
+def checkpoint_flat(payload, flags):
+    """The flat fp32 weights to evaluate: the raw master, or with
+    --use_moving_average the checkpoint's weight moving average — never a
+    silent fallback from one to the other."""
+    if not getattr(flags, "use_moving_average", False):
+        return payload["flat_master"]
+    if payload.get("flat_ema") is None:
+        raise ValueError(
+            "--use_moving_average: this checkpoint carries no weight moving "
+            "average; train with --moving_average_decay D (0 < D < 1) to "
+            "write one")
+    return payload["flat_ema"]
+
+
 def evaluate_resident(dataset, flags, writer=None):
     """--device_data poll loop: `dataset` is a DeviceDataSet already on the
     evaluator's device (uploaded once, before the loop); the model, its
@@ -78,7 +92,7 @@ def evaluate_resident(dataset, flags, writer=None):
                     ev = DeviceEvaluator(model, dataset,
                                          flags.eval_batch_size, device)
                     model_name = name
-                fp.load_flat(payload["flat_master"])
+                fp.load_flat(checkpoint_flat(payload, flags))
                 print('Succesfully loaded model from %s at step=%s.' %
                       (Supervisor.latest_checkpoint(flags.checkpoint_dir)[1], step),
                       flush=True)
@@ -121,6 +135,9 @@ def evaluate(dataset, flags, writer=None):
         if restored is not None:
             step, payload = restored
             if step != last_step:
+                ema_flat = (checkpoint_flat(payload, flags)
+                            if getattr(flags, "use_moving_average", False)
+                            else None)
                 model = build_model(payload.get("model", flags.model),
                                     seed=payload.get("seed", 66478),
                                     compute_dtype=dtype).to(device)
@@ -134,7 +151,9 @@ def evaluate(dataset, flags, writer=None):
                 # (round-1 built shadows ad hoc without shadows_T and fell
                 # onto the non-transposed GEMMs)
                 from ..parallel import FlatParams
-                FlatParams(model, device=device, compute_dtype=dtype)
+                fp = FlatParams(model, device=device, compute_dtype=dtype)
+                if ema_flat is not None:
+                    fp.load_flat(ema_flat)
                 print('Succesfully loaded model from %s at step=%s.' %
                       (Supervisor.latest_checkpoint(flags.checkpoint_dir)[1], step),
                       flush=True)

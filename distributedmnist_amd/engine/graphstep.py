@@ -90,10 +90,13 @@ class GraphedStep:
         # eager path zeroes at step START); the graphed protocol zeroes at
         # step END (SGD tail), so establish its invariant once here
         t.fp.flat_grad.zero_()
-        # snapshot state: the warmup iterations below really train
+        # snapshot state: the warmup iterations below really train (and
+        # move the weight moving average)
         master0 = t.fp.flat_master.clone()
         mom0 = (t.flat_momentum.clone()
                 if getattr(t, "flat_momentum", None) is not None else None)
+        ema0 = (t.flat_ema.clone()
+                if getattr(t, "flat_ema", None) is not None else None)
         t.model.set_step_dev(self.step_dev)
 
         if self.split and self._fused is not None:
@@ -214,6 +217,8 @@ class GraphedStep:
                 t.fp.flat_master.copy_(master0)
                 if mom0 is not None:
                     t.flat_momentum.copy_(mom0)
+                if ema0 is not None:
+                    t.flat_ema.copy_(ema0)
                 t.fp.sync_shadow()
                 t.model.set_step(t.step)
             except Exception:
@@ -227,6 +232,8 @@ class GraphedStep:
         t.fp.flat_master.copy_(master0)
         if mom0 is not None:
             t.flat_momentum.copy_(mom0)
+        if ema0 is not None:
+            t.flat_ema.copy_(ema0)
         t.fp.sync_shadow()
         self._prime(t.step)
         torch.cuda.synchronize()
@@ -284,7 +291,9 @@ class GraphedStep:
                                self.lr_scale_dev, self.dc_keep,
                                t.flags.seed, self.step_dev,
                                momentum=t.flat_momentum,
-                               mu=t.flags.momentum, zero_grad=True)
+                               mu=t.flags.momentum, zero_grad=True,
+                               ema=getattr(t, "flat_ema", None),
+                               ema_decay=getattr(t, "ema_decay", 0.0))
         if fp._t_pairs:
             # transposes + step/LR advance in ONE dispatch
             self._ext.transpose_bf16_batch_adv(

@@ -143,6 +143,26 @@ class Trainer:
             dist.broadcast(self.fp.flat_master, src=0)
             self.fp.sync_shadow()
             dist.barrier()
+        # --moving_average_decay D > 0: a twin model whose flat_master IS the
+        # weight moving average (TensorFlow ExponentialMovingAverage with
+        # num_updates; the reference's variable_averages argument).  The SGD
+        # kernel updates it in its own pass; evaluation runs on the twin.
+        # A pure function of the master sequence: identical on every rank,
+        # no collective.
+        self.ema_decay = float(getattr(flags, "moving_average_decay", 0.0)
+                               or 0.0)
+        if not 0.0 <= self.ema_decay < 1.0:
+            raise ValueError("--moving_average_decay must lie in [0, 1), "
+                             f"got {self.ema_decay}")
+        self.ema_model = self.ema_fp = self.flat_ema = None
+        if self.ema_decay > 0:
+            self.ema_model = build_model(
+                flags.model, seed=flags.seed,
+                compute_dtype=self.compute_dtype).to(self.device)
+            self.ema_fp = FlatParams(self.ema_model, device=self.device,
+                                     compute_dtype=self.compute_dtype)
+            self.flat_ema = self.ema_fp.flat_master
+            self.flat_ema.copy_(self.fp.flat_master)
 
     # ------------------------------------------------------------------
     def to_device(self, images, labels):
@@ -385,7 +405,8 @@ class Trainer:
                                            and not self._dc_pre) else None),
                     seed=flags.seed, offset=lr_step,
                     shadow=self.fp.flat_shadow,
-                    momentum=self.flat_momentum, mu=flags.momentum)
+                    momentum=self.flat_momentum, mu=flags.momentum,
+                    ema=self.flat_ema, ema_decay=self.ema_decay)
         self.fp.refresh_transposes()
         self.num_contributors = contributors
 
@@ -395,14 +416,26 @@ class Trainer:
         shard of the held-out set (make_eval_dataset)."""
         from .device_eval import DeviceEvaluator
         sharded = self.world > 1 and dist.is_initialized()
+        # with a weight moving average the evaluator reads the twin
         self.evaluator = DeviceEvaluator(
-            self.model, ds, self.flags.eval_batch_size, self.device,
+            self.eval_model, ds, self.flags.eval_batch_size, self.device,
             rank=self.rank, world=self.world if sharded else 1)
         return self.evaluator
 
+    @property
+    def eval_model(self):
+        """The model held-out evaluation reads: the moving-average twin
+        under --moving_average_decay, the live model otherwise."""
+        return self.ema_model if self.ema_model is not None else self.model
+
     def evaluate_now(self, writer=None):
-        """One held-out evaluation of the current weights; the precision
-        rides on the following step lines."""
+        """One held-out evaluation of the current weights (of their moving
+        average under --moving_average_decay); the precision rides on the
+        following step lines."""
+        if self.ema_fp is not None:
+            # bring the twin's compute copies (bf16 shadow + transposed
+            # weights) up to flat_ema: once per evaluation, never per step
+            self.ema_fp.publish()
         res = self.evaluator.run()
         self.test_acc = res.precision
         self.eval_history.append((self.step, res.precision, res.loss))
@@ -430,6 +463,16 @@ class Trainer:
                     and payload.get("flat_momentum") is not None):
                 self.flat_momentum.copy_(
                     payload["flat_momentum"].to(self.device))
+            if self.flat_ema is not None:
+                if payload.get("flat_ema") is not None:
+                    self.flat_ema.copy_(payload["flat_ema"].to(self.device))
+                else:
+                    log.warning(
+                        "checkpoint at step %d carries no weight moving "
+                        "average (it was written without "
+                        "--moving_average_decay): starting the average from "
+                        "the restored weights", step0)
+                    self.flat_ema.copy_(self.fp.flat_master)
             self.step = step0
             if self.is_chief:
                 log.info("Restored checkpoint at step %d", step0)
@@ -528,6 +571,8 @@ class Trainer:
             "flat_master": self.fp.flat_master.detach().cpu().clone(),
             "flat_momentum": (self.flat_momentum.detach().cpu().clone()
                               if self.flat_momentum is not None else None),
+            "flat_ema": (self.flat_ema.detach().cpu().clone()
+                         if self.flat_ema is not None else None),
             "model_state": {k: v.cpu() for k, v in
                             self.fp.state_dict_params().items()},
             "model": self.flags.model,

@@ -161,7 +161,8 @@ def softmax_xent_fwd(logits, labels):
 def sgd_step(master, grad, lr: float, grad_scale: float = 1.0,
              drop_connect_keep: float | None = None,
              gen: torch.Generator | None = None, shadow=None,
-             momentum=None, mu: float = 0.0):
+             momentum=None, mu: float = 0.0, ema=None,
+             ema_decay: float = 0.0, offset: int = 0):
     """In-place w -= lr * grad_scale * (g or momentum-filtered g).
 
     drop_connect_keep: if set, per-element Bernoulli(keep) mask on the grad
@@ -171,6 +172,10 @@ def sgd_step(master, grad, lr: float, grad_scale: float = 1.0,
     (the reference used plain GradientDescentOptimizer; momentum is the
     north-star's optional extension).
     shadow: optional flat low-precision copy refreshed after the update.
+    ema/ema_decay/offset: optional moving average of the weights
+    (TensorFlow's ExponentialMovingAverage with num_updates): update
+    k = offset + 1 does e -= (1 - d_k)*(e - w_new), d_k = min(ema_decay,
+    (1 + k)/(10 + k)), everything in fp32.
     """
     g = grad.float() * grad_scale
     if drop_connect_keep is not None:
@@ -181,9 +186,23 @@ def sgd_step(master, grad, lr: float, grad_scale: float = 1.0,
         momentum.mul_(mu).add_(g)
         g = momentum
     master.add_(g, alpha=-lr)
+    if ema is not None:
+        ema.sub_((ema - master) * ema_weight(ema_decay, offset))
     if shadow is not None:
         shadow.copy_(master.to(shadow.dtype))
     return master
+
+
+def ema_weight(ema_decay: float, offset: int) -> float:
+    """1 - d_k of update k = offset + 1, in numpy.float32 (the arithmetic
+    of sgd_step_kernel_ema)."""
+    if not 0.0 <= ema_decay < 1.0:
+        raise ValueError(f"ema_decay must lie in [0, 1), got {ema_decay}")
+    import numpy as np
+    k = np.float32(int(offset) + 1)
+    d = min(np.float32(ema_decay),
+            (np.float32(1) + k) / (np.float32(10) + k))
+    return float(np.float32(1) - d)
 
 
 # ---------------------------------------------------------------------------

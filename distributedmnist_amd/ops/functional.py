@@ -275,20 +275,27 @@ def softmax_eval(logits: torch.Tensor, labels: torch.Tensor,
 def sgd_step(master: torch.Tensor, grad: torch.Tensor, lr: float,
              grad_scale: float = 1.0, drop_connect_keep=None,
              seed: int = 0, offset: int = 0, shadow=None,
-             momentum=None, mu: float = 0.0):
+             momentum=None, mu: float = 0.0, ema=None,
+             ema_decay: float = 0.0):
     """Fused flat SGD apply: master -= lr*scale*(grad [* bernoulli(keep)]).
 
     Optionally refreshes the bf16 `shadow` copy (one kernel on GPU).
     Reference semantics: GradientDescentOptimizer + drop_connect mask with NO
     rescale (distributed_train.py:176,414-416).
+    `ema` (optional fp32, master's layout) is moved towards the new master
+    in the same pass: e -= (1 - d_k)*(e - w), d_k = min(ema_decay,
+    (1 + k)/(10 + k)), k = offset + 1 (ops/cpu_ref.py::sgd_step).
     """
+    if ema is not None and not 0.0 <= ema_decay < 1.0:
+        raise ValueError(f"ema_decay must lie in [0, 1), got {ema_decay}")
     if master.is_cuda:
         _C.ext().sgd_step(master, grad,
                           shadow if shadow is not None else master,
                           shadow is not None, float(lr), float(grad_scale),
                           -1.0 if drop_connect_keep is None else float(drop_connect_keep),
                           int(seed), int(offset),
-                          momentum=momentum, mu=float(mu))
+                          momentum=momentum, mu=float(mu), ema=ema,
+                          ema_decay=float(ema_decay))
     else:
         gen = None
         if drop_connect_keep is not None:
@@ -296,4 +303,5 @@ def sgd_step(master: torch.Tensor, grad: torch.Tensor, lr: float,
             gen.manual_seed((seed * 0x9E3779B97F4A7C15 + offset) % (2**63))
         cpu_ref.sgd_step(master, grad, lr, grad_scale,
                          drop_connect_keep, gen, shadow,
-                         momentum=momentum, mu=mu)
+                         momentum=momentum, mu=mu, ema=ema,
+                         ema_decay=ema_decay, offset=offset)

@@ -56,6 +56,7 @@ class FlatParams:
             # LDS staging instead of scatter transposes every K-step
             self.shadow_T = {}
             self._t_pairs = []
+            self._t_slices = []  # (flat offset, K, N) of each pair's source
             for n in getattr(model, "TRANSPOSED_WEIGHTS", []):
                 v = model.shadows[n]
                 v2 = v.reshape(-1, v.shape[-1])        # [K][N] k-major
@@ -63,6 +64,8 @@ class FlatParams:
                                 dtype=compute_dtype, device=device)
                 self.shadow_T[n] = t
                 self._t_pairs.append((v2, t))
+                self._t_slices.append((self.offsets[names.index(n)],
+                                       v2.shape[0], v2.shape[1]))
             model.shadows_T = self.shadow_T
             self.refresh_transposes()
         else:
@@ -70,6 +73,7 @@ class FlatParams:
             model.shadows_T = {}
             self.shadow_T = {}
             self._t_pairs = []
+            self._t_slices = []
 
     def zero_grad(self):
         self.flat_grad.zero_()
@@ -95,6 +99,22 @@ class FlatParams:
         if self.flat_shadow is not None:
             self.flat_shadow.copy_(self.flat_master.to(self.flat_shadow.dtype))
             self.refresh_transposes()
+
+    def publish(self):
+        """sync_shadow() for a flat_master that something other than the
+        SGD kernel wrote (the weight moving average): on the GPU in bf16 ONE
+        ema_publish launch — flat shadow and every transposed copy straight
+        from the fp32 buffer, no torch op, no allocation."""
+        if (self.flat_shadow is not None and self.flat_shadow.is_cuda
+                and self.flat_shadow.dtype == torch.bfloat16):
+            from .. import _C
+            _C.ext().ema_publish(self.flat_master, self.flat_shadow,
+                                 [o for o, _, _ in self._t_slices],
+                                 [r for _, r, _ in self._t_slices],
+                                 [c for _, _, c in self._t_slices],
+                                 [t for _, t in self._t_pairs])
+        else:
+            self.sync_shadow()
 
     def refresh_transposes(self):
         if not self._t_pairs:

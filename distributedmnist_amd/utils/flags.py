@@ -14,6 +14,18 @@ import argparse
 import os
 
 
+def _decay(text: str) -> float:
+    """--moving_average_decay: a float in [0, 1)."""
+    try:
+        v = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a number: {text!r}")
+    if not 0.0 <= v < 1.0:  # also refuses nan
+        raise argparse.ArgumentTypeError(
+            f"must lie in [0, 1), got {text}")
+    return v
+
+
 def build_train_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="MI355X-native distributed MNIST training")
     # --- reference-compatible flags (distributed_train.py:36-99) ---
@@ -114,6 +126,14 @@ def build_train_parser() -> argparse.ArgumentParser:
                         "--interval_method")
     p.add_argument("--eval_batch_size", type=int, default=1000,
                    help="chunk size of the in-training evaluation")
+    p.add_argument("--moving_average_decay", type=_decay, default=0.0,
+                   metavar="D",
+                   help="D in (0, 1): keep an exponential moving average of "
+                        "the weights (update k uses min(D, (1+k)/(10+k)), "
+                        "TensorFlow's ExponentialMovingAverage with "
+                        "num_updates), updated inside the SGD kernel, saved "
+                        "in the checkpoint as flat_ema and used by "
+                        "--eval_every_steps; 0 = off")
     return p
 
 
@@ -136,6 +156,11 @@ def build_eval_parser() -> argparse.ArgumentParser:
                         "built once, checkpoints loaded in place)")
     p.add_argument("--eval_batch_size", type=int, default=1000,
                    help="chunk size of the --device_data evaluation")
+    p.add_argument("--use_moving_average", action="store_true",
+                   help="evaluate the checkpoint's weight moving average "
+                        "(flat_ema, written by training runs with "
+                        "--moving_average_decay) instead of the raw weights; "
+                        "an error on checkpoints without one")
     p.add_argument("--confusion", action="store_true",
                    help="with --device_data: also save "
                         "eval_dir/confusion-<step>.npy and log per-class "
