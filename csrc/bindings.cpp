@@ -28,6 +28,28 @@ hipStream_t cur_stream() {
 
 int cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// Zeroed per-device workspace of a kernel that keeps self-resetting state
+// (partials, tickets) between launches: allocated on the first call per
+// device, which must therefore run outside graph capture.  Each op owns its
+// slots (one launch at a time per device and op); the vectors are leaked on
+// purpose, so no tensor is freed after the runtime has shut down.
+using WorkspaceSlots = std::vector<torch::Tensor>;
+
+torch::Tensor& device_workspace(WorkspaceSlots& slots,
+                                const torch::Tensor& like, int64_t numel,
+                                at::ScalarType dtype, hipStream_t s,
+                                const char* op, const char* capture_msg) {
+  int dev = like.get_device();
+  TORCH_CHECK(dev >= 0 && dev < (int)slots.size(), op, ": bad device index");
+  if (!slots[dev].defined()) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    hipStreamIsCapturing(s, &cap);
+    TORCH_CHECK(cap == hipStreamCaptureStatusNone, capture_msg);
+    slots[dev] = torch::zeros({numel}, like.options().dtype(dtype));
+  }
+  return slots[dev];
+}
+
 int pick_splitk(int mtiles, int ntiles, int ksteps) {
   int tiles = mtiles * ntiles;
   if (tiles >= 256 || ksteps <= 1) return 1;
@@ -148,6 +170,14 @@ torch::Tensor linear_act_fwd_impl(torch::Tensor x, torch::Tensor w,
   if (const char* e = getenv("DMNIST_FC_TILE")) big = atoi(e) >= 128;
   auto s = cur_stream();
   bool bt = wT.has_value() && wT->defined();
+  if (bt) {
+    // pre-transposed weight copy [N][K] -> vector B staging (B_NMAJ)
+    CHECK_BF16((*wT)); CHECK_CONTIG((*wT));
+    TORCH_CHECK(wT->size(0) == N && wT->size(1) == K, "wT shape mismatch");
+    p.B = bf16_ptr(*wT); p.ldb = K;
+  } else {
+    p.B = bf16_ptr(w); p.ldb = N;
+  }
   // split-K forward for grid-starved shapes (fc1 fwd @B=1024: 128 blocks
   // = half the chip idle): each k-slice writes its own fp32 [M][N] plane
   // (deterministic — no atomics), a fused epilogue sums planes + applies
@@ -176,18 +206,12 @@ torch::Tensor linear_act_fwd_impl(torch::Tensor x, torch::Tensor w,
     const char* fe = getenv("DMNIST_FC_FIXUP");
     bool fixup = fe && atoi(fe) != 0 && N % 8 == 0;
     if (fixup) {
-      static std::vector<torch::Tensor>* ws = new std::vector<torch::Tensor>(64);
-      int dev = x.get_device();
-      TORCH_CHECK(dev >= 0 && dev < 64, "linear_act_fwd: bad device index");
-      if (!(*ws)[dev].defined()) {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        hipStreamIsCapturing(s, &cap);
-        TORCH_CHECK(cap == hipStreamCaptureStatusNone,
-                    "linear_act_fwd: first split-K call on a device allocates "
-                    "its ticket workspace and must run outside graph capture");
-        (*ws)[dev] = torch::zeros({256}, x.options().dtype(at::kInt));
-      }
-      p.tickets = reinterpret_cast<unsigned*>((*ws)[dev].data_ptr<int>());
+      static auto* ws = new WorkspaceSlots(64);
+      auto& tickets = device_workspace(
+          *ws, x, 256, at::kInt, s, "linear_act_fwd",
+          "linear_act_fwd: first split-K call on a device allocates "
+          "its ticket workspace and must run outside graph capture");
+      p.tickets = reinterpret_cast<unsigned*>(tickets.data_ptr<int>());
       p.Y = bf16_mut(y);
       p.relu = relu ? 1 : 0;
     }
@@ -241,6 +265,64 @@ torch::Tensor linear_act_fwd_dev(torch::Tensor x, torch::Tensor w,
                              offset_dev.data_ptr<long>(), wT);
 }
 
+// --------------------------------------------------------------------------
+// Linear backward steps.  Each route decision lives in ONE function here; the
+// composite (autograd path) and the fine-grained ops of the hand-scheduled
+// fused step (engine/fused_step.py) both call it.
+// --------------------------------------------------------------------------
+// dyeff = dy masked by relu/dropout (recovered from sign(y)), db += column
+// sums.  Without a mask dyeff IS dy (no allocation) and y is not read.
+torch::Tensor mask_step(const torch::Tensor& dy, const torch::Tensor& y,
+                        bool relu, double p_keep, float* db, hipStream_t s) {
+  int B = dy.size(0), N = dy.size(1);
+  bool mask = relu || p_keep < 1.0;
+  torch::Tensor dyeff = mask ? torch::empty_like(dy) : dy;
+  launch_relu_drop_bwd(bf16_ptr(dy), mask ? bf16_ptr(y) : bf16_ptr(dy),
+                       bf16_mut(dyeff), db, B, N, (float)(1.0 / p_keep),
+                       mask ? 1 : 0, s);
+  return dyeff;
+}
+
+// dW[K,N] += x^T @ dyeff  (fp32; route and split from linear_dw_plan)
+void linear_dw_step(const torch::Tensor& x, const torch::Tensor& dyeff,
+                    void* dw, hipStream_t s) {
+  int B = x.size(0), K = x.size(1), N = dyeff.size(1);
+  GemmParams p{};
+  p.A = bf16_ptr(x); p.B = bf16_ptr(dyeff);
+  p.C = dw;
+  p.M = K; p.N = N; p.K = B;
+  p.lda = K;  // A_T: A[m][k'] = x[k'*lda + m]
+  p.ldb = N; p.ldc = N;
+  launch_linear_dw(p, K, N, B, s);
+}
+
+// out[B,K] = dyeff[B,N] @ w[K,N]^T: the block every dX GEMM shares; the
+// fused variants add only their epilogue fields
+GemmParams dx_params(const torch::Tensor& dyeff, const torch::Tensor& w,
+                     void* out) {
+  int B = dyeff.size(0), N = dyeff.size(1), K = w.size(0);
+  GemmParams p{};
+  p.A = bf16_ptr(dyeff); p.B = bf16_ptr(w);
+  p.C = out;
+  p.M = B; p.N = K; p.K = N;
+  p.lda = N; p.ldb = N; p.ldc = K;  // B_NMAJ: Bs[n'][k'] = w[n'*N + k']
+  p.splitk = 1;
+  return p;
+}
+
+// plain 64/128 tile choice of a dX GEMM: 128-tiles once they fill a grid
+bool dx_big_tiles(const GemmParams& p) {
+  return cdiv(p.M, 128) * cdiv(p.N, 128) >= 128;
+}
+
+torch::Tensor linear_dx_step(const torch::Tensor& dyeff,
+                             const torch::Tensor& w, hipStream_t s) {
+  auto dx = torch::empty({dyeff.size(0), w.size(0)}, dyeff.options());
+  GemmParams p = dx_params(dyeff, w, dx.data_ptr());
+  (dx_big_tiles(p) ? gemm_dx_128 : gemm_dx_64)(p, s);
+  return dx;
+}
+
 // core backward; when dw/db are passed they are accumulated into
 // (pre-zeroed fp32 bucket views — the direct-grad path); else allocated.
 std::vector<torch::Tensor> linear_act_bwd_impl(torch::Tensor dy, torch::Tensor x,
@@ -251,50 +333,18 @@ std::vector<torch::Tensor> linear_act_bwd_impl(torch::Tensor dy, torch::Tensor x
   CHECK_CUDA(dy); CHECK_BF16(dy); CHECK_CONTIG(dy);
   CHECK_BF16(x); CHECK_CONTIG(x);
   CHECK_BF16(w); CHECK_CONTIG(w);
-  int B = x.size(0), K = x.size(1), N = w.size(1);
+  int K = x.size(1), N = w.size(1);
   auto s = cur_stream();
   if (!db.defined())
     db = torch::zeros({N}, x.options().dtype(at::kFloat));
   CHECK_F32(db); CHECK_CONTIG(db);
-  torch::Tensor dyeff;
-  bool mask = relu || p_keep < 1.0;
-  if (mask) {
-    dyeff = torch::empty_like(dy);
-    launch_relu_drop_bwd(bf16_ptr(dy), bf16_ptr(y), bf16_mut(dyeff),
-                         db.data_ptr<float>(), B, N,
-                         (float)(1.0 / p_keep), 1, s);
-  } else {
-    dyeff = dy;
-    launch_relu_drop_bwd(bf16_ptr(dy), bf16_ptr(y), bf16_mut(dyeff),
-                         db.data_ptr<float>(), B, N, 1.0f, 0, s);
-  }
-  // dW[K,N] = x^T @ dyeff  (fp32 split-K atomics)
+  auto dyeff = mask_step(dy, y, relu, p_keep, db.data_ptr<float>(), s);
   if (!dw.defined())
     dw = torch::zeros({K, N}, x.options().dtype(at::kFloat));
   CHECK_F32(dw); CHECK_CONTIG(dw);
-  {
-    GemmParams p{};
-    p.A = bf16_ptr(x); p.B = bf16_ptr(dyeff);
-    p.C = dw.data_ptr();
-    p.M = K; p.N = N; p.K = B;
-    p.lda = K;  // A_T: A[m][k'] = x[k'*lda + m]
-    p.ldb = N; p.ldc = N;
-    launch_linear_dw(p, K, N, B, s);
-  }
-  torch::Tensor dx;
-  if (need_dx) {
-    dx = torch::empty({B, K}, x.options());
-    GemmParams p{};
-    p.A = bf16_ptr(dyeff); p.B = bf16_ptr(w);
-    p.C = dx.data_ptr();
-    p.M = B; p.N = K; p.K = N;
-    p.lda = N; p.ldb = N; p.ldc = K;  // B_NMAJ: Bs[n'][k'] = w[n'*N + k']
-    p.splitk = 1;
-    bool big = cdiv(B, 128) * cdiv(K, 128) >= 128;
-    (big ? gemm_dx_128 : gemm_dx_64)(p, s);
-  } else {
-    dx = torch::empty({0}, x.options());
-  }
+  linear_dw_step(x, dyeff, dw.data_ptr(), s);
+  auto dx = need_dx ? linear_dx_step(dyeff, w, s)
+                    : torch::empty({0}, x.options());
   return {dx, dw, db};
 }
 
@@ -371,79 +421,89 @@ std::vector<torch::Tensor> conv_pool_fwd(torch::Tensor x, torch::Tensor w,
   return {y, amax};
 }
 
-std::vector<torch::Tensor> conv_pool_bwd_impl(torch::Tensor dy, torch::Tensor x,
-                                              torch::Tensor w, torch::Tensor y,
-                                              torch::Tensor amax, bool need_dx,
-                                              torch::Tensor dw, torch::Tensor db) {
-  CHECK_CUDA(dy); CHECK_BF16(dy); CHECK_CONTIG(dy);
-  CHECK_BF16(x); CHECK_CONTIG(x); CHECK_BF16(w); CHECK_CONTIG(w);
-  int NB = x.size(0), H = x.size(1), W = x.size(2), Cin = x.size(3);
-  int Cout = w.size(3);
-  int Ho = H / 2, Wo = W / 2;
-  auto s = cur_stream();
-  // 1) scatter pooled grad (relu-masked) back to conv-output positions
-  auto dact = torch::empty({NB, H, W, Cout}, x.options());
-  if (!db.defined())
-    db = torch::zeros({Cout}, x.options().dtype(at::kFloat));
-  CHECK_F32(db); CHECK_CONTIG(db);
-  launch_pool_bwd_scatter(bf16_ptr(dy), bf16_ptr(y),
-                          amax.data_ptr<uint8_t>(), bf16_mut(dact),
-                          db.data_ptr<float>(), NB * Ho * Wo, Cout, H, W, Wo,
-                          s);
-  // 2) dW[(khkw,ci), co] = sum_pixels x_shift * dact  (im2col^T GEMM)
-  if (!dw.defined())
-    dw = torch::zeros({5, 5, Cin, Cout}, x.options().dtype(at::kFloat));
-  CHECK_F32(dw); CHECK_CONTIG(dw);
-  {
-    GemmParams p{};
-    p.A = bf16_ptr(x); p.B = bf16_ptr(dact);
-    p.C = dw.data_ptr();
-    p.M = 25 * Cin; p.N = Cout; p.K = NB * H * W;
-    p.ldb = Cout; p.ldc = Cout;
-    p.CB = NB; p.CH = H; p.CW = W; p.Cin = Cin; p.Cout = Cout;
-    if (Cin == 1 && H <= 28 && W <= 28 && Cout <= 32 &&
-        !getenv("DMNIST_DW1_SLAB")) {
-      launch_conv1_dw_direct(bf16_ptr(x), bf16_ptr(dact),
-                             dw.data_ptr<float>(), NB, H, W, Cout, s);
-    } else if (Cin == 1 && conv1_slab_supported(H, W, Cin, Cout)) {
-      launch_conv1_dw_slab(bf16_ptr(x), bf16_ptr(dact), dw.data_ptr<float>(),
-                           NB, H, W, Cout, s);
-    } else if (Cin == 1) {
-      // single 32x32 tile: target ~2048 blocks so the latency-bound gather
-      // k-chain is short and the chip stays full
-      p.splitk = std::min(cdiv(p.K, 64), 2048);
-      conv1_dw_gemm(p, s);
-    } else if (conv_slab_supported(H, W, Cin, Cout) &&
-               ((dw_tr_level() == 0 && NB >= 2048) || getenv("DMNIST_DW_G"))) {
-      // per-image-group slab dW: wins when the flush atomics amortize over
-      // >=4 images/block; below that the implicit-GEMM form is faster
-      launch_conv_dw_slab(bf16_ptr(x), bf16_ptr(dact), dw.data_ptr<float>(),
-                          NB, H, W, Cin, Cout, s);
-    } else if (conv2_dw_slab_route(H, W, Cin, Cout)) {
-      launch_conv2_dw_slab(bf16_ptr(x), bf16_ptr(dact), dw.data_ptr<float>(),
-                           NB, s);
-    } else {
-      int tiles = cdiv(p.M, 128) * cdiv(p.N, 64);
-      // total blocks target (DMNIST_DW_BLOCKS sweeps it): at BK=32 the
-      // small-batch optimum is 1024 blocks (63 vs 76 us @1024), large
-      // batches want 2048 (tools/dwsweep.py)
-      int want = p.K <= 262144 ? 1024 : 2048;
-      if (const char* e = getenv("DMNIST_DW_BLOCKS")) want = atoi(e);
-      p.splitk = std::min(cdiv(p.K, 64), std::max(1, want / tiles));
-      if (dw_tr_enabled() && Cin % 8 == 0 && Cout % 64 == 0)
-        conv_dw_tr(p, s);
-      else
-        conv_dw_gemm(p, s);
+// --------------------------------------------------------------------------
+// Conv backward steps, shared like the linear ones above.
+// --------------------------------------------------------------------------
+// scatter the pooled grad (relu-masked) back to conv-output positions
+// [NB][H][W][C]; db += the conv bias grad
+torch::Tensor pool_scatter_step(const torch::Tensor& dy, const torch::Tensor& y,
+                                const torch::Tensor& amax, float* db, int H,
+                                int W, hipStream_t s) {
+  int NB = dy.size(0), Ho = dy.size(1), Wo = dy.size(2), C = dy.size(3);
+  auto dact = torch::empty({NB, H, W, C}, dy.options());
+  launch_pool_bwd_scatter(bf16_ptr(dy), bf16_ptr(y), amax.data_ptr<uint8_t>(),
+                          bf16_mut(dact), db, NB * Ho * Wo, C, H, W, Wo, s);
+  return dact;
+}
+
+// THE conv dW route: dw[(khkw,ci), co] += sum_pixels x_shift * dact.  Both
+// conv_dw_into and the composite conv_pool_bwd come through here.  The
+// DMNIST_DW_SPREAD contention probe (atomics redirected to a throwaway
+// scratch: dw is NOT produced) therefore applies to both; before the ladder
+// had one copy, only conv_dw_into redirected.
+void route_conv_dw(const torch::Tensor& x, const torch::Tensor& dact,
+                   float* dw, int NB, int H, int W, int Cin, int Cout,
+                   hipStream_t s) {
+  GemmParams p{};
+  p.A = bf16_ptr(x); p.B = bf16_ptr(dact);
+  p.C = dw;
+  p.M = 25 * Cin; p.N = Cout; p.K = NB * H * W;
+  p.ldb = Cout; p.ldc = Cout;
+  p.CB = NB; p.CH = H; p.CW = W; p.Cin = Cin; p.Cout = Cout;
+  if (Cin == 1 && H <= 28 && W <= 28 && Cout <= 32 &&
+      !getenv("DMNIST_DW1_SLAB")) {
+    launch_conv1_dw_direct(bf16_ptr(x), bf16_ptr(dact), dw, NB, H, W, Cout,
+                           s);
+  } else if (Cin == 1 && conv1_slab_supported(H, W, Cin, Cout)) {
+    launch_conv1_dw_slab(bf16_ptr(x), bf16_ptr(dact), dw, NB, H, W, Cout, s);
+  } else if (Cin == 1) {
+    // single 32x32 tile: target ~2048 blocks so the latency-bound gather
+    // k-chain is short and the chip stays full
+    p.splitk = std::min(cdiv(p.K, 64), 2048);
+    conv1_dw_gemm(p, s);
+  } else if (conv_slab_supported(H, W, Cin, Cout) &&
+             ((dw_tr_level() == 0 && NB >= 2048) || getenv("DMNIST_DW_G"))) {
+    // per-image-group slab dW: wins when the flush atomics amortize over
+    // >=4 images/block; below that the implicit-GEMM form is faster
+    launch_conv_dw_slab(bf16_ptr(x), bf16_ptr(dact), dw, NB, H, W, Cin, Cout,
+                        s);
+  } else if (conv2_dw_slab_route(H, W, Cin, Cout)) {
+    launch_conv2_dw_slab(bf16_ptr(x), bf16_ptr(dact), dw, NB, s);
+  } else {
+    int tiles = cdiv(p.M, 128) * cdiv(p.N, 64);
+    // total blocks target (DMNIST_DW_BLOCKS sweeps it): at BK=32 the
+    // small-batch optimum is 1024 blocks (63 vs 76 us @1024), large
+    // batches want 2048 (tools/dwsweep.py)
+    int want = p.K <= 262144 ? 1024 : 2048;
+    if (const char* e = getenv("DMNIST_DW_BLOCKS")) want = atoi(e);
+    p.splitk = std::min(cdiv(p.K, 64), std::max(1, want / tiles));
+    if (getenv("DMNIST_DW_SPREAD")) {
+      // contention probe: atomics land in a throwaway 16-plane scratch
+      static torch::Tensor scratch;
+      int64_t need = 16LL * p.M * p.N;
+      if (!scratch.defined() || scratch.numel() < need)
+        scratch = torch::zeros({need}, dact.options().dtype(at::kFloat));
+      p.C = scratch.data_ptr();
+      p.offset = 1;
     }
+    if (dw_tr_enabled() && Cin % 8 == 0 && Cout % 64 == 0)
+      conv_dw_tr(p, s);
+    else
+      conv_dw_gemm(p, s);
   }
-  torch::Tensor dx;
-  if (need_dx && conv_slab_supported(H, W, Cin, Cout)) {
-    dx = torch::empty({NB, H, W, Cin}, x.options());
+}
+
+// conv dX: the per-image LDS slab where it fits, the implicit GEMM elsewhere
+torch::Tensor conv_dx_step(const torch::Tensor& dact, const torch::Tensor& w,
+                           int Cin, hipStream_t s) {
+  int NB = dact.size(0), H = dact.size(1), W = dact.size(2),
+      Cout = dact.size(3);
+  auto dx = torch::empty({NB, H, W, Cin}, dact.options());
+  if (conv_slab_supported(H, W, Cin, Cout)) {
     launch_conv_dx_slab(bf16_ptr(dact), bf16_ptr(w), bf16_mut(dx), NB, H, W,
                         Cin, Cout, s);
-  } else if (need_dx) {
+  } else {
     TORCH_CHECK(Cout % 32 == 0, "conv_dx requires Cout%32==0");
-    dx = torch::empty({NB, H, W, Cin}, x.options());
     GemmParams p{};
     p.A = bf16_ptr(dact); p.B = bf16_ptr(w);
     p.C = dx.data_ptr();
@@ -452,9 +512,29 @@ std::vector<torch::Tensor> conv_pool_bwd_impl(torch::Tensor dy, torch::Tensor x,
     p.CB = NB; p.CH = H; p.CW = W; p.Cin = Cin; p.Cout = Cout;
     p.splitk = 1;
     conv_dx_gemm(p, s);
-  } else {
-    dx = torch::empty({0}, x.options());
   }
+  return dx;
+}
+
+std::vector<torch::Tensor> conv_pool_bwd_impl(torch::Tensor dy, torch::Tensor x,
+                                              torch::Tensor w, torch::Tensor y,
+                                              torch::Tensor amax, bool need_dx,
+                                              torch::Tensor dw, torch::Tensor db) {
+  CHECK_CUDA(dy); CHECK_BF16(dy); CHECK_CONTIG(dy);
+  CHECK_BF16(x); CHECK_CONTIG(x); CHECK_BF16(w); CHECK_CONTIG(w);
+  int NB = x.size(0), H = x.size(1), W = x.size(2), Cin = x.size(3);
+  int Cout = w.size(3);
+  auto s = cur_stream();
+  if (!db.defined())
+    db = torch::zeros({Cout}, x.options().dtype(at::kFloat));
+  CHECK_F32(db); CHECK_CONTIG(db);
+  auto dact = pool_scatter_step(dy, y, amax, db.data_ptr<float>(), H, W, s);
+  if (!dw.defined())
+    dw = torch::zeros({5, 5, Cin, Cout}, x.options().dtype(at::kFloat));
+  CHECK_F32(dw); CHECK_CONTIG(dw);
+  route_conv_dw(x, dact, dw.data_ptr<float>(), NB, H, W, Cin, Cout, s);
+  auto dx = need_dx ? conv_dx_step(dact, w, Cin, s)
+                    : torch::empty({0}, x.options());
   return {dx, dw, db};
 }
 
@@ -477,49 +557,27 @@ torch::Tensor conv_pool_bwd_into(torch::Tensor dy, torch::Tensor x,
 // --------------------------------------------------------------------------
 // Fine-grained backward pieces for the hand-scheduled fused step
 // (engine/fused_step.py): the composite linear_act_bwd/conv_pool_bwd above
-// stay for the autograd path; these let dW run on a side stream while the
-// dX chain proceeds.
+// stay for the autograd path; these expose the same *_step functions one at
+// a time, so dW can run on a side stream while the dX chain proceeds.
 // --------------------------------------------------------------------------
 torch::Tensor mask_db(torch::Tensor dy, torch::Tensor y, bool relu,
                       double p_keep, torch::Tensor db_out) {
   CHECK_CUDA(dy); CHECK_BF16(dy); CHECK_CONTIG(dy);
   CHECK_F32(db_out); CHECK_CONTIG(db_out);
-  int B = dy.size(0), N = dy.size(1);
-  auto s = cur_stream();
-  bool mask = relu || p_keep < 1.0;
-  torch::Tensor dyeff = mask ? torch::empty_like(dy) : dy;
-  launch_relu_drop_bwd(bf16_ptr(dy), mask ? bf16_ptr(y) : bf16_ptr(dy),
-                       bf16_mut(dyeff), db_out.data_ptr<float>(), B, N,
-                       (float)(1.0 / p_keep), mask ? 1 : 0, s);
-  return dyeff;
+  return mask_step(dy, y, relu, p_keep, db_out.data_ptr<float>(),
+                   cur_stream());
 }
 
 void linear_dw_into(torch::Tensor x, torch::Tensor dyeff,
                     torch::Tensor dw_out) {
   CHECK_BF16(x); CHECK_CONTIG(x); CHECK_BF16(dyeff); CHECK_CONTIG(dyeff);
   CHECK_F32(dw_out);
-  int B = x.size(0), K = x.size(1), N = dyeff.size(1);
-  GemmParams p{};
-  p.A = bf16_ptr(x); p.B = bf16_ptr(dyeff);
-  p.C = dw_out.data_ptr();
-  p.M = K; p.N = N; p.K = B;
-  p.lda = K; p.ldb = N; p.ldc = N;
-  launch_linear_dw(p, K, N, B, cur_stream());
+  linear_dw_step(x, dyeff, dw_out.data_ptr(), cur_stream());
 }
 
 torch::Tensor linear_dx(torch::Tensor dyeff, torch::Tensor w) {
   CHECK_BF16(dyeff); CHECK_CONTIG(dyeff); CHECK_BF16(w); CHECK_CONTIG(w);
-  int B = dyeff.size(0), N = dyeff.size(1), K = w.size(0);
-  auto dx = torch::empty({B, K}, dyeff.options());
-  GemmParams p{};
-  p.A = bf16_ptr(dyeff); p.B = bf16_ptr(w);
-  p.C = dx.data_ptr();
-  p.M = B; p.N = K; p.K = N;
-  p.lda = N; p.ldb = N; p.ldc = K;
-  p.splitk = 1;
-  bool big = cdiv(B, 128) * cdiv(K, 128) >= 128;
-  (big ? gemm_dx_128 : gemm_dx_64)(p, cur_stream());
-  return dx;
+  return linear_dx_step(dyeff, w, cur_stream());
 }
 
 torch::Tensor linear_dx_unpool(torch::Tensor dyeff, torch::Tensor w,
@@ -532,16 +590,11 @@ torch::Tensor linear_dx_unpool(torch::Tensor dyeff, torch::Tensor w,
   // the conv bias grad — dact [B][2Ho][2Wo][C] comes straight out of the
   // GEMM (replaces linear_dx + pool_scatter on the backward critical path).
   CHECK_BF16(dyeff); CHECK_CONTIG(dyeff); CHECK_BF16(w); CHECK_CONTIG(w);
-  int B = dyeff.size(0), N = dyeff.size(1), K = w.size(0);
+  int B = dyeff.size(0), K = w.size(0);
   TORCH_CHECK(K == Ho * Wo * C, "linear_dx_unpool: K != Ho*Wo*C");
   auto dact = torch::empty({B, 2 * (int)Ho, 2 * (int)Wo, (int)C},
                            dyeff.options());
-  GemmParams p{};
-  p.A = bf16_ptr(dyeff); p.B = bf16_ptr(w);
-  p.C = dact.data_ptr();
-  p.M = B; p.N = K; p.K = N;
-  p.lda = N; p.ldb = N; p.ldc = K;
-  p.splitk = 1;
+  GemmParams p = dx_params(dyeff, w, dact.data_ptr());
   p.CHo = Ho; p.CWo = Wo; p.Cout = C;
   p.amax = amax.data_ptr<uint8_t>();
   p.db = db_out.defined() ? db_out.data_ptr<float>() : nullptr;
@@ -590,12 +643,7 @@ torch::Tensor linear_dx_pooled(torch::Tensor dyeff, torch::Tensor w,
   TORCH_CHECK(tile == 0 || tile == 64 || tile == 128,
               "linear_dx_pooled: tile is 0, 64 or 128");
   auto gp = torch::empty({B, (int)Ho, (int)Wo, (int)C}, dyeff.options());
-  GemmParams p{};
-  p.A = bf16_ptr(dyeff); p.B = bf16_ptr(w);
-  p.C = gp.data_ptr();
-  p.M = B; p.N = K; p.K = N;
-  p.lda = N; p.ldb = N; p.ldc = K;
-  p.splitk = 1;
+  GemmParams p = dx_params(dyeff, w, gp.data_ptr());
   p.CHo = Ho; p.CWo = Wo; p.Cout = C;
   p.amax = amax.data_ptr<uint8_t>();
   p.db = db_out.defined() ? db_out.data_ptr<float>() : nullptr;
@@ -618,20 +666,14 @@ torch::Tensor linear_dx_mask(torch::Tensor dyeff, torch::Tensor w,
   // replaces linear_dx + the standalone mask_db pass (fc2-dX -> dyeff1).
   CHECK_BF16(dyeff); CHECK_CONTIG(dyeff); CHECK_BF16(w); CHECK_CONTIG(w);
   CHECK_BF16(actm); CHECK_CONTIG(actm);
-  int B = dyeff.size(0), N = dyeff.size(1), K = w.size(0);
+  int B = dyeff.size(0), K = w.size(0);
   TORCH_CHECK(actm.size(0) == B && actm.size(1) == K, "actm shape mismatch");
   auto dx = torch::empty({B, K}, dyeff.options());
-  GemmParams p{};
-  p.A = bf16_ptr(dyeff); p.B = bf16_ptr(w);
-  p.C = dx.data_ptr();
-  p.M = B; p.N = K; p.K = N;
-  p.lda = N; p.ldb = N; p.ldc = K;
-  p.splitk = 1;
+  GemmParams p = dx_params(dyeff, w, dx.data_ptr());
   p.p_keep = (float)(1.0 / p_keep);  // kernel multiplies by the inverse
   p.actm = bf16_ptr(actm);
   p.db = db_out.defined() ? db_out.data_ptr<float>() : nullptr;
-  bool big = cdiv(B, 128) * cdiv(K, 128) >= 128;
-  (big ? gemm_dx_mask_128 : gemm_dx_mask_64)(p, cur_stream());
+  (dx_big_tiles(p) ? gemm_dx_mask_128 : gemm_dx_mask_64)(p, cur_stream());
   return dx;
 }
 
@@ -639,65 +681,14 @@ torch::Tensor pool_scatter(torch::Tensor dy, torch::Tensor y,
                            torch::Tensor amax, torch::Tensor db_out,
                            int64_t H, int64_t W) {
   CHECK_BF16(dy); CHECK_CONTIG(dy);
-  int NB = dy.size(0), Ho = dy.size(1), Wo = dy.size(2), C = dy.size(3);
-  auto dact = torch::empty({NB, (int)H, (int)W, C}, dy.options());
-  launch_pool_bwd_scatter(bf16_ptr(dy), bf16_ptr(y),
-                          amax.data_ptr<uint8_t>(), bf16_mut(dact),
-                          db_out.data_ptr<float>(), NB * Ho * Wo, C, H, W,
-                          Wo, cur_stream());
-  return dact;
+  return pool_scatter_step(dy, y, amax, db_out.data_ptr<float>(), (int)H,
+                           (int)W, cur_stream());
 }
 
 void conv_dw_into(torch::Tensor x, torch::Tensor dact, torch::Tensor dw_out) {
   CHECK_BF16(x); CHECK_CONTIG(x); CHECK_BF16(dact); CHECK_CONTIG(dact);
-  int NB = x.size(0), H = x.size(1), W = x.size(2), Cin = x.size(3);
-  int Cout = dact.size(3);
-  auto s = cur_stream();
-  GemmParams p{};
-  p.A = bf16_ptr(x); p.B = bf16_ptr(dact);
-  p.C = dw_out.data_ptr();
-  p.M = 25 * Cin; p.N = Cout; p.K = NB * H * W;
-  p.ldb = Cout; p.ldc = Cout;
-  p.CB = NB; p.CH = H; p.CW = W; p.Cin = Cin; p.Cout = Cout;
-  if (Cin == 1 && H <= 28 && W <= 28 && Cout <= 32 &&
-      !getenv("DMNIST_DW1_SLAB")) {
-    launch_conv1_dw_direct(bf16_ptr(x), bf16_ptr(dact),
-                           dw_out.data_ptr<float>(), NB, H, W, Cout, s);
-  } else if (Cin == 1 && conv1_slab_supported(H, W, Cin, Cout)) {
-    launch_conv1_dw_slab(bf16_ptr(x), bf16_ptr(dact),
-                         dw_out.data_ptr<float>(), NB, H, W, Cout, s);
-  } else if (Cin == 1) {
-    p.splitk = std::min(cdiv(p.K, 64), 2048);
-    conv1_dw_gemm(p, s);
-  } else if (conv_slab_supported(H, W, Cin, Cout) &&
-             ((dw_tr_level() == 0 && NB >= 2048) || getenv("DMNIST_DW_G"))) {
-    launch_conv_dw_slab(bf16_ptr(x), bf16_ptr(dact), dw_out.data_ptr<float>(),
-                        NB, H, W, Cin, Cout, s);
-  } else if (conv2_dw_slab_route(H, W, Cin, Cout)) {
-    launch_conv2_dw_slab(bf16_ptr(x), bf16_ptr(dact),
-                         dw_out.data_ptr<float>(), NB, s);
-  } else {
-    int tiles = cdiv(p.M, 128) * cdiv(p.N, 64);
-    // total blocks target (DMNIST_DW_BLOCKS sweeps it): at BK=32 the
-    // small-batch optimum is 1024 blocks (63 vs 76 us @1024), large
-    // batches want 2048 (tools/dwsweep.py)
-    int want = p.K <= 262144 ? 1024 : 2048;
-    if (const char* e = getenv("DMNIST_DW_BLOCKS")) want = atoi(e);
-    p.splitk = std::min(cdiv(p.K, 64), std::max(1, want / tiles));
-    if (getenv("DMNIST_DW_SPREAD")) {
-      // contention probe: atomics land in a throwaway 16-plane scratch
-      static torch::Tensor scratch;
-      int64_t need = 16LL * p.M * p.N;
-      if (!scratch.defined() || scratch.numel() < need)
-        scratch = torch::zeros({need}, dact.options().dtype(at::kFloat));
-      p.C = scratch.data_ptr();
-      p.offset = 1;
-    }
-    if (dw_tr_enabled() && Cin % 8 == 0 && Cout % 64 == 0)
-      conv_dw_tr(p, s);
-    else
-      conv_dw_gemm(p, s);
-  }
+  route_conv_dw(x, dact, dw_out.data_ptr<float>(), x.size(0), x.size(1),
+                x.size(2), x.size(3), dact.size(3), cur_stream());
 }
 
 void conv1_dw_pooled(torch::Tensor x, torch::Tensor dyp, torch::Tensor am,
@@ -729,25 +720,7 @@ void conv1_dw_pooled(torch::Tensor x, torch::Tensor dyp, torch::Tensor am,
 
 torch::Tensor conv_dx(torch::Tensor dact, torch::Tensor w, int64_t Cin) {
   CHECK_BF16(dact); CHECK_CONTIG(dact); CHECK_BF16(w); CHECK_CONTIG(w);
-  int NB = dact.size(0), H = dact.size(1), W = dact.size(2),
-      Cout = dact.size(3);
-  auto s = cur_stream();
-  auto dx = torch::empty({NB, H, W, (int)Cin}, dact.options());
-  if (conv_slab_supported(H, W, Cin, Cout)) {
-    launch_conv_dx_slab(bf16_ptr(dact), bf16_ptr(w), bf16_mut(dx), NB, H, W,
-                        Cin, Cout, s);
-  } else {
-    TORCH_CHECK(Cout % 32 == 0, "conv_dx requires Cout%32==0");
-    GemmParams p{};
-    p.A = bf16_ptr(dact); p.B = bf16_ptr(w);
-    p.C = dx.data_ptr();
-    p.M = NB * H * W; p.N = Cin; p.K = 25 * Cout;
-    p.ldc = Cin;
-    p.CB = NB; p.CH = H; p.CW = W; p.Cin = Cin; p.Cout = Cout;
-    p.splitk = 1;
-    conv_dx_gemm(p, s);
-  }
-  return dx;
+  return conv_dx_step(dact, w, (int)Cin, cur_stream());
 }
 
 // conv2 backward from the pooled gradient gp [NB][7][7][64] and the pool
@@ -818,19 +791,12 @@ std::vector<torch::Tensor> softmax_xent_fwd(torch::Tensor logits,
   // launch per step.  Its workspace (per-block partials + ticket counter)
   // is allocated and zeroed once per device; the counter resets itself.
   auto out = torch::empty({2}, logits.options().dtype(at::kFloat));
-  static std::vector<torch::Tensor>* ws = new std::vector<torch::Tensor>(64);
-  int dev = logits.get_device();
-  TORCH_CHECK(dev >= 0 && dev < 64, "softmax_xent: bad device index");
-  if (!(*ws)[dev].defined()) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    hipStreamIsCapturing(cur_stream(), &cap);
-    TORCH_CHECK(cap == hipStreamCaptureStatusNone,
-                "softmax_xent_fwd: first call on a device allocates its "
-                "workspace and must run outside graph capture");
-    (*ws)[dev] = torch::zeros({2 * SOFTMAX_MAX_BLOCKS + 1},
-                              logits.options().dtype(at::kFloat));
-  }
-  float* part = (*ws)[dev].data_ptr<float>();
+  static auto* ws = new WorkspaceSlots(64);
+  float* part = device_workspace(
+      *ws, logits, 2 * SOFTMAX_MAX_BLOCKS + 1, at::kFloat, cur_stream(),
+      "softmax_xent",
+      "softmax_xent_fwd: first call on a device allocates its "
+      "workspace and must run outside graph capture").data_ptr<float>();
   unsigned* ticket = reinterpret_cast<unsigned*>(part + 2 * SOFTMAX_MAX_BLOCKS);
   float* dbp = nullptr;
   if (db_out.has_value() && db_out->defined())
@@ -857,6 +823,13 @@ static float* ema_ptr(const c10::optional<torch::Tensor>& ema,
   return ema->data_ptr<float>();
 }
 
+// optional momentum buffer of the SGD pass: nullptr = plain SGD
+static float* momentum_ptr(const c10::optional<torch::Tensor>& momentum) {
+  if (!momentum.has_value() || !momentum->defined()) return nullptr;
+  CHECK_F32((*momentum)); CHECK_CONTIG((*momentum));
+  return momentum->data_ptr<float>();
+}
+
 void sgd_step(torch::Tensor master, torch::Tensor grad, torch::Tensor shadow,
               bool has_shadow, double lr, double scale, double dc_keep,
               int64_t seed, int64_t offset,
@@ -864,11 +837,7 @@ void sgd_step(torch::Tensor master, torch::Tensor grad, torch::Tensor shadow,
               c10::optional<torch::Tensor> ema, double ema_decay) {
   CHECK_CUDA(master); CHECK_F32(master); CHECK_CONTIG(master);
   CHECK_F32(grad); CHECK_CONTIG(grad);
-  float* mom = nullptr;
-  if (momentum.has_value() && momentum->defined()) {
-    CHECK_F32((*momentum)); CHECK_CONTIG((*momentum));
-    mom = momentum->data_ptr<float>();
-  }
+  float* mom = momentum_ptr(momentum);
   float* emap = ema_ptr(ema, master, ema_decay);
   launch_sgd_step(master.data_ptr<float>(), grad.data_ptr<float>(),
                   has_shadow ? bf16_mut(shadow) : nullptr,
@@ -888,11 +857,7 @@ void sgd_step_dev(torch::Tensor master, torch::Tensor grad,
   CHECK_CUDA(master); CHECK_F32(master); CHECK_CONTIG(master);
   CHECK_F32(grad); CHECK_CONTIG(grad);
   CHECK_F32(lr_scale_dev);
-  float* mom = nullptr;
-  if (momentum.has_value() && momentum->defined()) {
-    CHECK_F32((*momentum)); CHECK_CONTIG((*momentum));
-    mom = momentum->data_ptr<float>();
-  }
+  float* mom = momentum_ptr(momentum);  // same fp32 + contiguity checks
   launch_sgd_step_dev(master.data_ptr<float>(), grad.data_ptr<float>(),
                       has_shadow ? bf16_mut(shadow) : nullptr,
                       has_shadow ? 1 : 0, master.numel(),
@@ -931,18 +896,27 @@ void ema_publish(torch::Tensor ema, torch::Tensor shadow,
                      (int)nt, cur_stream());
 }
 
-void transpose_bf16_batch(std::vector<torch::Tensor> srcs,
-                          std::vector<torch::Tensor> dsts) {
+// checks up to 4 (src [R][C], dst [C][R]) bf16 pairs and fills their
+// descriptors; returns the pair count
+static int fill_transposes(TransposeDesc (&d)[4],
+                           std::vector<torch::Tensor>& srcs,
+                           std::vector<torch::Tensor>& dsts) {
   TORCH_CHECK(srcs.size() == dsts.size() && srcs.size() <= 4,
               "up to 4 transpose pairs");
-  TransposeDesc d[4];
   for (size_t i = 0; i < srcs.size(); ++i) {
     CHECK_BF16(srcs[i]); CHECK_CONTIG(srcs[i]);
     CHECK_BF16(dsts[i]); CHECK_CONTIG(dsts[i]);
     d[i] = {bf16_ptr(srcs[i]), bf16_mut(dsts[i]),
             (int)srcs[i].size(0), (int)srcs[i].size(1)};
   }
-  launch_transpose_bf16_batch(d, (int)srcs.size(), cur_stream());
+  return (int)srcs.size();
+}
+
+void transpose_bf16_batch(std::vector<torch::Tensor> srcs,
+                          std::vector<torch::Tensor> dsts) {
+  TransposeDesc d[4];
+  int n = fill_transposes(d, srcs, dsts);
+  launch_transpose_bf16_batch(d, n, cur_stream());
 }
 
 void transpose_bf16_batch_adv(std::vector<torch::Tensor> srcs,
@@ -953,17 +927,10 @@ void transpose_bf16_batch_adv(std::vector<torch::Tensor> srcs,
                               double inv_contrib) {
   // graph-tail variant: the batched transposes + the device step/LR
   // advance in ONE dispatch (step_advance folded into the last launch)
-  TORCH_CHECK(srcs.size() == dsts.size() && srcs.size() <= 4,
-              "up to 4 transpose pairs");
   TransposeDesc d[4];
-  for (size_t i = 0; i < srcs.size(); ++i) {
-    CHECK_BF16(srcs[i]); CHECK_CONTIG(srcs[i]);
-    CHECK_BF16(dsts[i]); CHECK_CONTIG(dsts[i]);
-    d[i] = {bf16_ptr(srcs[i]), bf16_mut(dsts[i]),
-            (int)srcs[i].size(0), (int)srcs[i].size(1)};
-  }
+  int n = fill_transposes(d, srcs, dsts);  // pair count, bf16, contiguity
   launch_transpose_bf16_batch_adv(
-      d, (int)srcs.size(), step_dev.data_ptr<long>(),
+      d, n, step_dev.data_ptr<long>(),
       lr_scale_dev.data_ptr<float>(), (float)lr0, (float)decay,
       (int)decay_steps, (float)inv_contrib, cur_stream());
 }
@@ -1001,10 +968,20 @@ void grad_mask(torch::Tensor g, double keep, int64_t seed, int64_t step,
                    cur_stream());
 }
 
-void batch_gather(torch::Tensor img_u8, torch::Tensor lab_u8,
-                  torch::Tensor lut, torch::Tensor x, torch::Tensor y,
-                  int64_t seed, int64_t step,
-                  c10::optional<torch::Tensor> step_dev) {
+// Argument checks shared by the three gathers of the device-resident uint8
+// set.  `op` prefixes every message; `pos` names the host position argument
+// ("step" / "start") whose device form is `pos_dev`.  A batch drawn from the
+// epoch permutation needs B <= N; a sequential chunk may run past N (the rows
+// past N are padding), so it sets chunk.  sd is the device position, or
+// nullptr when the host value is used.
+struct GatherArgs { int64_t N, B; const long* sd; };
+static GatherArgs check_gather(const char* op, const torch::Tensor& img_u8,
+                               const torch::Tensor& lab_u8,
+                               const torch::Tensor& lut,
+                               const torch::Tensor& x, const torch::Tensor& y,
+                               const char* pos, int64_t pos_host,
+                               const c10::optional<torch::Tensor>& pos_dev,
+                               bool chunk) {
   CHECK_CUDA(img_u8); CHECK_CONTIG(img_u8);
   CHECK_CUDA(lab_u8); CHECK_CONTIG(lab_u8);
   CHECK_CUDA(lut); CHECK_BF16(lut); CHECK_CONTIG(lut);
@@ -1012,120 +989,74 @@ void batch_gather(torch::Tensor img_u8, torch::Tensor lab_u8,
   CHECK_CUDA(y); CHECK_CONTIG(y);
   TORCH_CHECK(img_u8.scalar_type() == at::kByte &&
               lab_u8.scalar_type() == at::kByte,
-              "batch_gather: images/labels must be uint8");
-  TORCH_CHECK(y.scalar_type() == at::kLong, "batch_gather: y must be int64");
+              op, ": images/labels must be uint8");
+  TORCH_CHECK(y.scalar_type() == at::kLong, op, ": y must be int64");
   const int64_t N = lab_u8.numel(), B = y.numel();
-  TORCH_CHECK(N >= 1 && N < (int64_t(1) << 31),
-              "batch_gather: N out of range");
-  TORCH_CHECK(B >= 1 && B <= N, "batch_gather: batch size ", B,
-              " must be in [1, N=", N, "]");
-  TORCH_CHECK(img_u8.numel() == N * 784, "batch_gather: images must be [N,784]");
-  TORCH_CHECK(x.numel() == B * 784, "batch_gather: x must hold B*784 values");
-  TORCH_CHECK(lut.numel() == 256, "batch_gather: lut must have 256 entries");
+  TORCH_CHECK(N >= 1 && N < (int64_t(1) << 31), op, ": N out of range");
+  if (chunk) {
+    TORCH_CHECK(B >= 1 && B < (int64_t(1) << 31),
+                op, ": chunk size out of range");
+  } else {
+    TORCH_CHECK(B >= 1 && B <= N, op, ": batch size ", B,
+                " must be in [1, N=", N, "]");
+  }
+  TORCH_CHECK(img_u8.numel() == N * 784, op, ": images must be [N,784]");
+  TORCH_CHECK(x.numel() == B * 784, op, ": x must hold B*784 values");
+  TORCH_CHECK(lut.numel() == 256, op, ": lut must have 256 entries");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(img_u8.data_ptr()) % 8 == 0 &&
               reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
-              "batch_gather: images must be 8B- and x 16B-aligned");
+              op, ": images must be 8B- and x 16B-aligned");
   const long* sd = nullptr;
-  if (step_dev.has_value() && step_dev->defined()) {
-    TORCH_CHECK(step_dev->is_cuda() && step_dev->scalar_type() == at::kLong &&
-                step_dev->numel() >= 1, "batch_gather: step_dev must be a "
-                "device int64 tensor");
-    sd = step_dev->data_ptr<long>();
+  if (pos_dev.has_value() && pos_dev->defined()) {
+    TORCH_CHECK(pos_dev->is_cuda() && pos_dev->scalar_type() == at::kLong &&
+                pos_dev->numel() >= 1, op, ": ", pos,
+                "_dev must be a device int64 tensor");
+    sd = pos_dev->data_ptr<long>();
   } else {
-    TORCH_CHECK(step >= 0, "batch_gather: step must be >= 0");
+    TORCH_CHECK(pos_host >= 0, op, ": ", pos, " must be >= 0");
   }
+  return {N, B, sd};
+}
+
+void batch_gather(torch::Tensor img_u8, torch::Tensor lab_u8,
+                  torch::Tensor lut, torch::Tensor x, torch::Tensor y,
+                  int64_t seed, int64_t step,
+                  c10::optional<torch::Tensor> step_dev) {
+  GatherArgs a = check_gather("batch_gather", img_u8, lab_u8, lut, x, y,
+                              "step", step, step_dev, false);
   launch_batch_gather(img_u8.data_ptr<uint8_t>(), lab_u8.data_ptr<uint8_t>(),
                       bf16_ptr(lut), bf16_mut(x), y.data_ptr<long>(),
-                      (uint32_t)N, (uint32_t)B, (uint64_t)seed,
-                      (uint64_t)step, sd, cur_stream());
+                      (uint32_t)a.N, (uint32_t)a.B, (uint64_t)seed,
+                      (uint64_t)step, a.sd, cur_stream());
 }
 
 void batch_gather_aug(torch::Tensor img_u8, torch::Tensor lab_u8,
                       torch::Tensor lut, torch::Tensor table, torch::Tensor x,
                       torch::Tensor y, int64_t seed, int64_t step,
                       c10::optional<torch::Tensor> step_dev) {
-  CHECK_CUDA(img_u8); CHECK_CONTIG(img_u8);
-  CHECK_CUDA(lab_u8); CHECK_CONTIG(lab_u8);
-  CHECK_CUDA(lut); CHECK_BF16(lut); CHECK_CONTIG(lut);
   CHECK_CUDA(table); CHECK_CONTIG(table);
-  CHECK_CUDA(x); CHECK_BF16(x); CHECK_CONTIG(x);
-  CHECK_CUDA(y); CHECK_CONTIG(y);
-  TORCH_CHECK(img_u8.scalar_type() == at::kByte &&
-              lab_u8.scalar_type() == at::kByte,
-              "batch_gather_aug: images/labels must be uint8");
-  TORCH_CHECK(y.scalar_type() == at::kLong,
-              "batch_gather_aug: y must be int64");
   TORCH_CHECK(table.scalar_type() == at::kInt && table.dim() == 2 &&
               table.size(1) == 6 && table.size(0) >= 1 &&
               table.size(0) < (int64_t(1) << 31),
               "batch_gather_aug: table must be int32 [T >= 1, 6]");
-  const int64_t N = lab_u8.numel(), B = y.numel();
-  TORCH_CHECK(N >= 1 && N < (int64_t(1) << 31),
-              "batch_gather_aug: N out of range");
-  TORCH_CHECK(B >= 1 && B <= N, "batch_gather_aug: batch size ", B,
-              " must be in [1, N=", N, "]");
-  TORCH_CHECK(img_u8.numel() == N * 784,
-              "batch_gather_aug: images must be [N,784]");
-  TORCH_CHECK(x.numel() == B * 784,
-              "batch_gather_aug: x must hold B*784 values");
-  TORCH_CHECK(lut.numel() == 256,
-              "batch_gather_aug: lut must have 256 entries");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(img_u8.data_ptr()) % 8 == 0 &&
-              reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
-              "batch_gather_aug: images must be 8B- and x 16B-aligned");
-  const long* sd = nullptr;
-  if (step_dev.has_value() && step_dev->defined()) {
-    TORCH_CHECK(step_dev->is_cuda() && step_dev->scalar_type() == at::kLong &&
-                step_dev->numel() >= 1, "batch_gather_aug: step_dev must be "
-                "a device int64 tensor");
-    sd = step_dev->data_ptr<long>();
-  } else {
-    TORCH_CHECK(step >= 0, "batch_gather_aug: step must be >= 0");
-  }
+  GatherArgs a = check_gather("batch_gather_aug", img_u8, lab_u8, lut, x, y,
+                              "step", step, step_dev, false);
   launch_batch_gather_aug(img_u8.data_ptr<uint8_t>(),
                           lab_u8.data_ptr<uint8_t>(), bf16_ptr(lut),
                           table.data_ptr<int>(), (uint32_t)table.size(0),
-                          bf16_mut(x), y.data_ptr<long>(), (uint32_t)N,
-                          (uint32_t)B, (uint64_t)seed, (uint64_t)step, sd,
+                          bf16_mut(x), y.data_ptr<long>(), (uint32_t)a.N,
+                          (uint32_t)a.B, (uint64_t)seed, (uint64_t)step, a.sd,
                           cur_stream());
 }
 
 void range_gather(torch::Tensor img_u8, torch::Tensor lab_u8,
                   torch::Tensor lut, torch::Tensor x, torch::Tensor y,
                   int64_t start, c10::optional<torch::Tensor> start_dev) {
-  CHECK_CUDA(img_u8); CHECK_CONTIG(img_u8);
-  CHECK_CUDA(lab_u8); CHECK_CONTIG(lab_u8);
-  CHECK_CUDA(lut); CHECK_BF16(lut); CHECK_CONTIG(lut);
-  CHECK_CUDA(x); CHECK_BF16(x); CHECK_CONTIG(x);
-  CHECK_CUDA(y); CHECK_CONTIG(y);
-  TORCH_CHECK(img_u8.scalar_type() == at::kByte &&
-              lab_u8.scalar_type() == at::kByte,
-              "range_gather: images/labels must be uint8");
-  TORCH_CHECK(y.scalar_type() == at::kLong, "range_gather: y must be int64");
-  const int64_t N = lab_u8.numel(), B = y.numel();
-  TORCH_CHECK(N >= 1 && N < (int64_t(1) << 31),
-              "range_gather: N out of range");
-  // B > N is legal here: the rows past N are padding
-  TORCH_CHECK(B >= 1 && B < (int64_t(1) << 31),
-              "range_gather: chunk size out of range");
-  TORCH_CHECK(img_u8.numel() == N * 784, "range_gather: images must be [N,784]");
-  TORCH_CHECK(x.numel() == B * 784, "range_gather: x must hold B*784 values");
-  TORCH_CHECK(lut.numel() == 256, "range_gather: lut must have 256 entries");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(img_u8.data_ptr()) % 8 == 0 &&
-              reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
-              "range_gather: images must be 8B- and x 16B-aligned");
-  const long* sd = nullptr;
-  if (start_dev.has_value() && start_dev->defined()) {
-    TORCH_CHECK(start_dev->is_cuda() && start_dev->scalar_type() == at::kLong &&
-                start_dev->numel() >= 1, "range_gather: start_dev must be a "
-                "device int64 tensor");
-    sd = start_dev->data_ptr<long>();
-  } else {
-    TORCH_CHECK(start >= 0, "range_gather: start must be >= 0");
-  }
+  GatherArgs a = check_gather("range_gather", img_u8, lab_u8, lut, x, y,
+                              "start", start, start_dev, true);
   launch_range_gather(img_u8.data_ptr<uint8_t>(), lab_u8.data_ptr<uint8_t>(),
                       bf16_ptr(lut), bf16_mut(x), y.data_ptr<long>(),
-                      (uint32_t)N, (uint32_t)B, (uint64_t)start, sd,
+                      (uint32_t)a.N, (uint32_t)a.B, (uint64_t)start, a.sd,
                       cur_stream());
 }
 
@@ -1169,19 +1100,12 @@ void softmax_eval(torch::Tensor logits, torch::Tensor labels,
   // the kernel's own partial/ticket workspace (never the training
   // softmax's), allocated and zeroed once per device; the counter resets
   // itself
-  static std::vector<torch::Tensor>* ws = new std::vector<torch::Tensor>(64);
-  int dev = logits.get_device();
-  TORCH_CHECK(dev >= 0 && dev < 64, "softmax_eval: bad device index");
-  if (!(*ws)[dev].defined()) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    hipStreamIsCapturing(cur_stream(), &cap);
-    TORCH_CHECK(cap == hipStreamCaptureStatusNone,
-                "softmax_eval: first call on a device allocates its "
-                "workspace and must run outside graph capture");
-    (*ws)[dev] = torch::zeros({SOFTMAX_MAX_BLOCKS + 1},
-                              logits.options().dtype(at::kFloat));
-  }
-  float* part = (*ws)[dev].data_ptr<float>();
+  static auto* ws = new WorkspaceSlots(64);
+  float* part = device_workspace(
+      *ws, logits, SOFTMAX_MAX_BLOCKS + 1, at::kFloat, cur_stream(),
+      "softmax_eval",
+      "softmax_eval: first call on a device allocates its "
+      "workspace and must run outside graph capture").data_ptr<float>();
   unsigned* ticket = reinterpret_cast<unsigned*>(part + SOFTMAX_MAX_BLOCKS);
   launch_softmax_eval(bf16_ptr(logits), labels.data_ptr<long>(),
                       loss_sum.data_ptr<float>(), counts.data_ptr<int>(), pp,

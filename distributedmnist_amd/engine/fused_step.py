@@ -95,16 +95,53 @@ class FusedLeNetStep:
     def __call__(self, x, labels, step_dev):
         """One fwd+bwd; gradients land in the flat bucket.
         Returns (loss, mean_accuracy) device scalars."""
-        ext = self.ext
+        reduce_grads = self.overlap_allreduce
+        loss, acc, conv_in, self._keep = self._fc_part(x, labels, step_dev,
+                                                       reduce_grads)
+        self._conv_part(*conv_in)
+        if reduce_grads:
+            self.t.engine.wire_allreduce(self.conv_slice, start=0)
+        return loss, acc
+
+    # ------------------------------------------------------------------
+    # Two-stage form of the SAME schedule, for the two-graph split capture
+    # (graphstep.py): stage_fc ends with every fc gradient final (so the
+    # eager fc-slice all-reduce can launch between the graphs and overlap
+    # stage_conv's replay); stage_conv finishes the conv backward.  Both
+    # forms run _fc_part then _conv_part; here the collectives live OUTSIDE
+    # and the fc stage joins its side stream at the end so graph A's
+    # boundary is well-defined.
+    def stage_fc(self, x, labels, step_dev):
+        loss, acc, self._stash, self._keep = self._fc_part(
+            x, labels, step_dev, False)
+        s0, s1 = self._streams()
+        s0.wait_stream(s1)  # graph A boundary: fc grads complete
+        return loss, acc
+
+    def stage_conv(self):
+        self._conv_part(*self._stash)
+        self._keep2 = self._stash
+
+    def _gv(self, name):
+        return getattr(self.t.model, name).grad
+
+    def _streams(self):
+        """(s0, s1): the stream the body runs on RIGHT NOW and the dW side
+        stream (s0 itself in single-stream mode)."""
+        s0 = torch.cuda.current_stream()
+        return s0, (s0 if self.single_stream else self.side)
+
+    def _fc_part(self, x, labels, step_dev, reduce_fc):
+        """Forward, softmax, fc2 dW, fc2 dX+mask, fc1 dW, fc1 dX+poolmask.
+        reduce_fc issues the fc-slice all-reduce on s1 right after fc1 dW.
+        Returns (loss, acc, _conv_part's arguments, keep): keep holds every
+        tensor a side-stream op of either part reads, and the caller stores
+        it until the join (capture-safe)."""
+        ext, gv = self.ext, self._gv
         m = self.t.model
         sh, shT = m.shadows, m.shadows_T
         B = x.shape[0]
-
-        def gv(name):
-            return getattr(m, name).grad
-
-        s0 = torch.cuda.current_stream()
-        s1 = s0 if self.single_stream else self.side
+        s0, s1 = self._streams()
 
         # ---- forward (s0) ----
         y1, am1 = ext.conv_pool_fwd(x, sh["conv1_w"], m.conv1_b, None)
@@ -135,32 +172,34 @@ class FusedLeNetStep:
         self._fork(s1, s0)
         with torch.cuda.stream(s1):
             ext.linear_dw_into(h2, dyeff1, gv("fc1_w"))
-            if self.overlap_allreduce:
+            if reduce_fc:
                 # every fc gradient (fc2 via the earlier s1 work + the db's
                 # ordered by wait_stream) is final here
                 self.t.engine.wire_allreduce(self.fc_slice,
                                              start=self.fc_offset)
         # fc1 dX with the pool2 mask + conv2 db in the GEMM epilogue
         # (liveness rides in the amax byte, no y2 re-read); pool2 backward
-        # itself happens in the conv2 dW / dX slab staging
+        # itself happens in the conv2 dW / dX slab staging.  conv2_b is in
+        # the conv slice, reduced after the conv part in either form.
         g2 = self._fc1_dx(dyeff1, am2)
+        keep = (a1, h2, dyeff1, dl, y1, g2, am2)
+        return loss, acc, (x, y1, am1, g2, am2), keep
+
+    def _conv_part(self, x, y1, am1, g2, am2):
+        """conv2 dW (placed by overlap level), conv2 dX, conv1 dW+db, and
+        the s0 <- s1 join."""
+        s0, s1 = self._streams()
         sW = s1 if self.overlap_level >= 2 else s0  # conv2 dW placement
         if sW is not s0:
             self._fork(sW, s0)
         with torch.cuda.stream(sW):
             self._conv2_dw(y1, g2, am2)
         dxc = self._conv2_dx(g2, am2)
-
         # conv1 dW+db consume the POOLED gradient (pool1 backward fused in
         # the consumer; the 4x-size dact1 is never materialized)
-        ext.conv1_dw_pooled(x, dxc, am1, gv("conv1_w"), gv("conv1_b"))
-
+        self.ext.conv1_dw_pooled(x, dxc, am1, self._gv("conv1_w"),
+                                 self._gv("conv1_b"))
         self._fork(s0, s1)
-        if self.overlap_allreduce:
-            self.t.engine.wire_allreduce(self.conv_slice, start=0)
-        # keep the side-stream consumers alive until the join (capture-safe)
-        self._keep = (a1, h2, dyeff1, dl, y1, g2, am2)
-        return loss, acc
 
     # pool2 backward: g2 is the pooled gradient gp2 [B,7,7,64] (default) or,
     # with DMNIST_POOL2_FUSED=0, the dense dact2 [B,14,14,64]
@@ -182,73 +221,3 @@ class FusedLeNetStep:
         if self.pool2_fused:
             return self.ext.conv_dx_pooled(g2, am2, w, 32)
         return self.ext.conv_dx(g2, w, 32)
-
-    # ------------------------------------------------------------------
-    # Two-stage form of the SAME schedule, for the two-graph split capture
-    # (graphstep.py): stage_fc ends with every fc gradient final (so the
-    # eager fc-slice all-reduce can launch between the graphs and overlap
-    # stage_conv's replay); stage_conv finishes the conv backward.  The
-    # math and stream schedule per stage are identical to __call__ above —
-    # which stays the single-capture/eager body — except the collectives
-    # live OUTSIDE and the fc stage joins its side stream at the end so
-    # graph A's boundary is well-defined.
-    def stage_fc(self, x, labels, step_dev):
-        ext = self.ext
-        m = self.t.model
-        sh, shT = m.shadows, m.shadows_T
-        B = x.shape[0]
-
-        def gv(name):
-            return getattr(m, name).grad
-
-        s0 = torch.cuda.current_stream()
-        s1 = s0 if self.single_stream else self.side
-        y1, am1 = ext.conv_pool_fwd(x, sh["conv1_w"], m.conv1_b, None)
-        y2, am2 = ext.conv_pool_fwd(y1, sh["conv2_w"], m.conv2_b,
-                                    shT["conv2_w"])
-        h2 = y2.view(B, 7 * 7 * 64)
-        a1 = ext.linear_act_fwd_dev(h2, sh["fc1_w"], m.fc1_b, True,
-                                    self.p_keep, self.seed, step_dev,
-                                    shT["fc1_w"])
-        logits = ext.linear_act_fwd(a1, sh["fc2_w"], m.fc2_b, False, 1.0,
-                                    0, 0, shT["fc2_w"])
-        # inv_n folds the accuracy mean into the kernel: no scalar-divide
-        # launch per step; `acc` below is already the MEAN accuracy
-        loss, acc, dl = ext.softmax_xent_fwd(logits, labels,
-                                             db_out=gv("fc2_b"),
-                                             inv_n=1.0 / B)
-        self._fork(s1, s0)
-        with torch.cuda.stream(s1):
-            ext.linear_dw_into(a1, dl, gv("fc2_w"))
-        dyeff1 = ext.linear_dx_mask(dl, sh["fc2_w"], a1, gv("fc1_b"),
-                                    self.p_keep)
-        self._fork(s1, s0)
-        with torch.cuda.stream(s1):
-            ext.linear_dw_into(h2, dyeff1, gv("fc1_w"))
-        # fc1 dX + pool2 mask: conv2_b lands here (conv slice — reduced
-        # after graph B, so computing it early is safe)
-        g2 = self._fc1_dx(dyeff1, am2)
-        s0.wait_stream(s1)  # graph A boundary: fc grads complete
-        self._stash = (x, y1, am1, g2, am2)
-        self._keep = (a1, h2, dyeff1, dl)
-        return loss, acc
-
-    def stage_conv(self):
-        ext = self.ext
-        m = self.t.model
-
-        def gv(name):
-            return getattr(m, name).grad
-
-        x, y1, am1, g2, am2 = self._stash
-        s0 = torch.cuda.current_stream()
-        s1 = s0 if self.single_stream else self.side
-        sW = s1 if self.overlap_level >= 2 else s0  # conv2 dW placement
-        if sW is not s0:
-            self._fork(sW, s0)
-        with torch.cuda.stream(sW):
-            self._conv2_dw(y1, g2, am2)
-        dxc = self._conv2_dx(g2, am2)
-        ext.conv1_dw_pooled(x, dxc, am1, gv("conv1_w"), gv("conv1_b"))
-        self._fork(s0, s1)
-        self._keep2 = (g2, am2)
