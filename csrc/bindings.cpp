@@ -6,6 +6,10 @@
 #include <ATen/hip/HIPContext.h>
 #include <hip/hip_runtime.h>
 
+#include <atomic>
+#include <map>
+#include <tuple>
+
 #include "kernels.h"
 
 namespace {
@@ -48,6 +52,75 @@ torch::Tensor& device_workspace(WorkspaceSlots& slots,
     slots[dev] = torch::zeros({numel}, like.options().dtype(dtype));
   }
   return slots[dev];
+}
+
+// --------------------------------------------------------------------------
+// Deterministic mode (docs/KERNELS.md, "Deterministic mode").  A per-process
+// switch read on every call.  With it on, the gradient ops of the default
+// fused LeNet route launch their *_det sibling: blocks store private planes,
+// plane_reduce adds them in index order on the producer's stream and does the
+// one add into the bucket.  Ops whose route still needs float atomics across
+// blocks (or LDS float atomics) raise instead of running.
+// --------------------------------------------------------------------------
+std::atomic<bool> g_deterministic{false};
+bool det_on() { return g_deterministic.load(std::memory_order_relaxed); }
+
+[[noreturn]] void det_refuse(const char* op, const char* route) {
+  TORCH_CHECK(false, op, ": deterministic mode is on and this route is not "
+              "covered (", route, "); refusing to run it");
+  abort();
+}
+
+// One plane region per (device, site, destination size): the ops of one site
+// and size are ordered on a stream or graph (as the softmax workspace is), and
+// sites that run concurrently (conv2 dW on the side stream, the bias tails
+// while fc dW is in flight) never share a region.  Planes are never assumed
+// to hold anything: every element the reduction reads is stored in the same
+// step.  (Re)allocated only outside graph capture.
+enum DetSite { DET_SOFTMAX_DB = 0, DET_MASK_DB, DET_POOLED_DB, DET_FC_DW,
+               DET_CONV2_DW, DET_CONV1 };
+#define DET_MAX_BYTES (int64_t(1) << 30)
+using DetRegions = std::map<std::tuple<int, int, int64_t>, torch::Tensor>;
+DetRegions& det_regions() {
+  static auto* r = new DetRegions();  // leaked like the other workspaces
+  return *r;
+}
+
+float* det_region(DetSite site, const torch::Tensor& like, int64_t n,
+                  int64_t planes, hipStream_t s, const char* op,
+                  const char* setting) {
+  const int64_t need = planes * n;
+  TORCH_CHECK(need * 4 <= DET_MAX_BYTES, op, ": deterministic mode needs ",
+              planes, " planes of ", n, " floats (", need * 4,
+              " bytes), above the 1 GiB workspace limit; ", setting);
+  auto key = std::make_tuple((int)like.get_device(), (int)site, n);
+  auto& regions = det_regions();
+  auto it = regions.find(key);
+  if (it == regions.end() || it->second.numel() < need) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    hipStreamIsCapturing(s, &cap);
+    TORCH_CHECK(cap == hipStreamCaptureStatusNone, op,
+                ": deterministic-mode plane workspace is missing or too "
+                "small and cannot be allocated during graph capture; run the "
+                "op once outside capture first");
+    if (it != regions.end()) {
+      // a graph captured earlier may still hold the smaller region's address:
+      // it is retired, never freed
+      static auto* retired = new std::vector<torch::Tensor>();
+      retired->push_back(it->second);
+    }
+    regions[key] = torch::empty({need}, like.options().dtype(at::kFloat));
+    it = regions.find(key);
+  }
+  return it->second.data_ptr<float>();
+}
+
+void reduce_planes(const float* planes, float* out, int64_t n, int64_t stride,
+                   int P, hipStream_t s, bool store = false) {
+  PlaneReduceDesc d{};
+  d.planes = planes; d.out = out; d.n = n; d.stride = stride; d.P = P;
+  d.store = store ? 1 : 0;
+  launch_plane_reduce(&d, 1, s);
 }
 
 int pick_splitk(int mtiles, int ntiles, int ksteps) {
@@ -128,9 +201,28 @@ DwPlan linear_dw_plan(int K, int N, int B) {
   return old;
 }
 
-void launch_linear_dw(GemmParams& p, int K, int N, int B, hipStream_t s) {
+void launch_linear_dw(GemmParams& p, int K, int N, int B, hipStream_t s,
+                      const torch::Tensor& like) {
   DwPlan pl = linear_dw_plan(K, N, B);
   p.splitk = pl.splitk;
+  if (det_on() && pl.splitk > 1) {
+    // deterministic mode: one stored plane per k-slice, summed in slice
+    // order.  splitk == 1 launches below are already one writer per element.
+    const int64_t n = (int64_t)K * N;
+    float* planes = det_region(DET_FC_DW, like, n, pl.splitk, s,
+                               "linear_dw_into", "lower the split "
+                               "(DMNIST_DW_PLAN)");
+    float* out = reinterpret_cast<float*>(p.C);
+    if (pl.tr) {
+      p.det_planes = planes; p.det_stride = n;
+      gemm_dw_tr_det(p, pl.tbm, pl.bn, s);
+    } else {
+      p.C = planes;  // OUT_F32_SLICES: slice z at C + z*M*ldc
+      (pl.tbm == 128 ? gemm_dw_planes_128 : gemm_dw_planes_64)(p, s);
+    }
+    reduce_planes(planes, out, n, n, pl.splitk, s);
+    return;
+  }
   if (pl.tr) {
     bool sw = pl.splitk == 1 && ((uintptr_t)p.C & 15) == 0 && p.ldc % 4 == 0;
     gemm_dw_tr(p, pl.tbm, pl.bn, sw, s);
@@ -274,6 +366,9 @@ torch::Tensor linear_act_fwd_dev(torch::Tensor x, torch::Tensor w,
 // sums.  Without a mask dyeff IS dy (no allocation) and y is not read.
 torch::Tensor mask_step(const torch::Tensor& dy, const torch::Tensor& y,
                         bool relu, double p_keep, float* db, hipStream_t s) {
+  if (det_on())
+    det_refuse("mask_db / linear_act_bwd",
+               "relu_drop_bwd adds its column sums into db with float atomics");
   int B = dy.size(0), N = dy.size(1);
   bool mask = relu || p_keep < 1.0;
   torch::Tensor dyeff = mask ? torch::empty_like(dy) : dy;
@@ -293,7 +388,7 @@ void linear_dw_step(const torch::Tensor& x, const torch::Tensor& dyeff,
   p.M = K; p.N = N; p.K = B;
   p.lda = K;  // A_T: A[m][k'] = x[k'*lda + m]
   p.ldb = N; p.ldc = N;
-  launch_linear_dw(p, K, N, B, s);
+  launch_linear_dw(p, K, N, B, s, x);
 }
 
 // out[B,K] = dyeff[B,N] @ w[K,N]^T: the block every dX GEMM shares; the
@@ -429,6 +524,9 @@ std::vector<torch::Tensor> conv_pool_fwd(torch::Tensor x, torch::Tensor w,
 torch::Tensor pool_scatter_step(const torch::Tensor& dy, const torch::Tensor& y,
                                 const torch::Tensor& amax, float* db, int H,
                                 int W, hipStream_t s) {
+  if (det_on())
+    det_refuse("pool_scatter / conv_pool_bwd",
+               "pool_bwd_scatter adds db with float atomics");
   int NB = dy.size(0), Ho = dy.size(1), Wo = dy.size(2), C = dy.size(3);
   auto dact = torch::empty({NB, H, W, C}, dy.options());
   launch_pool_bwd_scatter(bf16_ptr(dy), bf16_ptr(y), amax.data_ptr<uint8_t>(),
@@ -444,6 +542,27 @@ torch::Tensor pool_scatter_step(const torch::Tensor& dy, const torch::Tensor& y,
 void route_conv_dw(const torch::Tensor& x, const torch::Tensor& dact,
                    float* dw, int NB, int H, int W, int Cin, int Cout,
                    hipStream_t s) {
+  if (det_on()) {
+    // deterministic mode covers the dense conv2 slab kernel in its shipped
+    // form (it shares its flush with the pooled one); every other conv dW
+    // route adds into dw with float atomics across blocks
+    bool slab = Cin != 1 && conv2_dw_slab_route(H, W, Cin, Cout) &&
+                !(conv_slab_supported(H, W, Cin, Cout) &&
+                  ((dw_tr_level() == 0 && NB >= 2048) ||
+                   getenv("DMNIST_DW_G"))) &&
+                !getenv("DMNIST_DW2_KHB") && !getenv("DMNIST_DW2_NBUF");
+    if (!slab)
+      det_refuse("conv_dw_into / conv_pool_bwd",
+                 "only the conv2 slab route (14x14, 32->64, no sweep "
+                 "switches) has a plane flush; this route uses float atomics");
+    if (NB <= 0) return;
+    int groups = conv2_dw_groups(NB);
+    float* planes = det_region(DET_CONV2_DW, x, CONV2_DET_PLANE, groups, s,
+                               "conv_dw_into", "raise DMNIST_DW2_G");
+    launch_conv2_dw_slab_det(bf16_ptr(x), bf16_ptr(dact), planes, NB, s);
+    reduce_planes(planes, dw, CONV2_DET_PLANE, CONV2_DET_PLANE, groups, s);
+    return;
+  }
   GemmParams p{};
   p.A = bf16_ptr(x); p.B = bf16_ptr(dact);
   p.C = dw;
@@ -590,6 +709,10 @@ torch::Tensor linear_dx_unpool(torch::Tensor dyeff, torch::Tensor w,
   // the conv bias grad — dact [B][2Ho][2Wo][C] comes straight out of the
   // GEMM (replaces linear_dx + pool_scatter on the backward critical path).
   CHECK_BF16(dyeff); CHECK_CONTIG(dyeff); CHECK_BF16(w); CHECK_CONTIG(w);
+  if (det_on())
+    det_refuse("linear_dx_unpool",
+               "the EPI_UNPOOL bias tail uses LDS and global float atomics; "
+               "use linear_dx_pooled");
   int B = dyeff.size(0), K = w.size(0);
   TORCH_CHECK(K == Ho * Wo * C, "linear_dx_unpool: K != Ho*Wo*C");
   auto dact = torch::empty({B, 2 * (int)Ho, 2 * (int)Wo, (int)C},
@@ -653,6 +776,23 @@ torch::Tensor linear_dx_pooled(torch::Tensor dyeff, torch::Tensor w,
                    ((uintptr_t)p.C & 15) == 0;
   bool big = cdiv(B, 128) * cdiv(K, 128) >= POOLED_DX_BIG_TILES;
   if (tile) big = tile == 128;
+  if (det_on() && p.db && B > 0) {
+    // deterministic mode: block row r stores its [K] column sums into plane
+    // r.  Two ordered stages (a single one would walk rows * Ho*Wo planes of
+    // C floats serially): T = sum over block rows, stored into the spare
+    // plane behind them; then K = (pixel, channel), so T read as [Ho*Wo][C]
+    // is the plane set of the C channel sums, added in pixel order into db
+    auto s = cur_stream();
+    int rows = cdiv(B, big ? 128 : 64);
+    float* planes = det_region(DET_POOLED_DB, dyeff, K, rows + 1, s,
+                               "linear_dx_pooled", "lower the batch size");
+    float* colsum = planes + (size_t)rows * K;
+    p.det_planes = planes; p.det_stride = K;
+    (big ? gemm_dx_poolmask_128_det : gemm_dx_poolmask_64_det)(p, s);
+    reduce_planes(planes, colsum, K, K, rows, s, /*store=*/true);
+    reduce_planes(colsum, p.db, C, C, (int)(Ho * Wo), s);
+    return gp;
+  }
   (big ? gemm_dx_poolmask_128 : gemm_dx_poolmask_64)(p, cur_stream());
   return gp;
 }
@@ -673,6 +813,18 @@ torch::Tensor linear_dx_mask(torch::Tensor dyeff, torch::Tensor w,
   p.p_keep = (float)(1.0 / p_keep);  // kernel multiplies by the inverse
   p.actm = bf16_ptr(actm);
   p.db = db_out.defined() ? db_out.data_ptr<float>() : nullptr;
+  if (det_on() && p.db && B > 0) {
+    // deterministic mode: one [K] plane of column sums per block row
+    auto s = cur_stream();
+    bool big = dx_big_tiles(p);
+    int rows = cdiv(B, big ? 128 : 64);
+    float* planes = det_region(DET_MASK_DB, dyeff, K, rows, s,
+                               "linear_dx_mask", "lower the batch size");
+    p.det_planes = planes; p.det_stride = K;
+    (big ? gemm_dx_mask_128_det : gemm_dx_mask_64_det)(p, s);
+    reduce_planes(planes, p.db, K, K, rows, s);
+    return dx;
+  }
   (dx_big_tiles(p) ? gemm_dx_mask_128 : gemm_dx_mask_64)(p, cur_stream());
   return dx;
 }
@@ -704,6 +856,36 @@ void conv1_dw_pooled(torch::Tensor x, torch::Tensor dyp, torch::Tensor am,
                   dyp.size(1) == H / 2 && dyp.size(2) == W / 2,
               "conv1_dw_pooled: LeNet conv1 shapes only");
   CHECK_CONTIG(am); CHECK_F32(dw_out); CHECK_CONTIG(dw_out);
+  if (det_on()) {
+    // deterministic mode: the MFMA kernel stores one 832-float plane (800 dW
+    // + 32 db) per block; both destinations are reduced in one launch
+    if (!(conv1_mfma_supported(H, W, 1, Cout) && conv1_mfma_enabled() &&
+          reinterpret_cast<uintptr_t>(x.data_ptr()) % 8 == 0))
+      det_refuse("conv1_dw_pooled",
+                 "the DMNIST_CONV1_VALU=1 / unaligned-x kernel flushes with "
+                 "float atomics");
+    TORCH_CHECK(dw_out.numel() == 25 * 32, "conv1_dw_pooled: dw size");
+    if (NB <= 0) return;
+    auto s = cur_stream();
+    int blocks = conv1_mfma_dw_blocks(NB);
+    float* planes = det_region(DET_CONV1, x, CONV1_DET_PLANE, blocks, s,
+                               "conv1_dw_pooled", "raise DMNIST_DW1_G");
+    launch_conv1_mfma_dw_det(bf16_ptr(x), bf16_ptr(dyp),
+                             am.data_ptr<uint8_t>(), planes, NB, s);
+    PlaneReduceDesc d[2] = {};
+    d[0].planes = planes; d[0].out = dw_out.data_ptr<float>();
+    d[0].n = 25 * 32; d[0].stride = CONV1_DET_PLANE; d[0].P = blocks;
+    int nd = 1;
+    if (db_out.defined()) {
+      CHECK_F32(db_out); CHECK_CONTIG(db_out);
+      TORCH_CHECK(db_out.numel() == 32, "conv1_dw_pooled: db size");
+      d[1].planes = planes + 25 * 32; d[1].out = db_out.data_ptr<float>();
+      d[1].n = 32; d[1].stride = CONV1_DET_PLANE; d[1].P = blocks;
+      nd = 2;
+    }
+    launch_plane_reduce(d, nd, s);
+    return;
+  }
   if (conv1_mfma_supported(H, W, 1, Cout) && conv1_mfma_enabled() &&
       reinterpret_cast<uintptr_t>(x.data_ptr()) % 8 == 0) {
     launch_conv1_mfma_dw(bf16_ptr(x), bf16_ptr(dyp), am.data_ptr<uint8_t>(),
@@ -765,6 +947,22 @@ void conv_dw_pooled_into(torch::Tensor x, torch::Tensor gp, torch::Tensor am,
               "conv_dw_pooled_into: x is [NB][14][14][32]");
   TORCH_CHECK(dw_out.numel() == 25 * 32 * 64, "conv_dw_pooled_into: dw size");
   TORCH_CHECK(((uintptr_t)x.data_ptr() & 15) == 0, "x 16 B alignment");
+  if (det_on()) {
+    // deterministic mode: one stored plane per image group, summed in group
+    // order; the reduction is given the true group count, so the planes of
+    // the blocks that pad the grid are neither written nor read
+    int NB = x.size(0);
+    if (NB <= 0) return;
+    auto s = cur_stream();
+    int groups = conv2_dw_groups(NB);
+    float* planes = det_region(DET_CONV2_DW, x, CONV2_DET_PLANE, groups, s,
+                               "conv_dw_pooled_into", "raise DMNIST_DW2_G");
+    launch_conv2_dw_slab_pooled_det(bf16_ptr(x), bf16_ptr(gp),
+                                    am.data_ptr<uint8_t>(), planes, NB, s);
+    reduce_planes(planes, dw_out.data_ptr<float>(), CONV2_DET_PLANE,
+                  CONV2_DET_PLANE, groups, s);
+    return;
+  }
   launch_conv2_dw_slab_pooled(bf16_ptr(x), bf16_ptr(gp),
                               am.data_ptr<uint8_t>(),
                               dw_out.data_ptr<float>(), (int)x.size(0),
@@ -801,9 +999,21 @@ std::vector<torch::Tensor> softmax_xent_fwd(torch::Tensor logits,
   float* dbp = nullptr;
   if (db_out.has_value() && db_out->defined())
     dbp = db_out->data_ptr<float>();
-  launch_softmax_xent(bf16_ptr(logits), labels.data_ptr<long>(),
-                      bf16_mut(dl), out.data_ptr<float>(), B, C, dbp,
-                      (float)inv_n, part, ticket, cur_stream());
+  if (det_on() && dbp && B > 0) {
+    // deterministic mode: one [C] plane of column sums per block
+    auto s = cur_stream();
+    int blocks = softmax_xent_blocks(B);
+    float* planes = det_region(DET_SOFTMAX_DB, logits, C, blocks, s,
+                               "softmax_xent_fwd", "lower the batch size");
+    launch_softmax_xent_det(bf16_ptr(logits), labels.data_ptr<long>(),
+                            bf16_mut(dl), out.data_ptr<float>(), B, C, planes,
+                            (float)inv_n, part, ticket, s);
+    reduce_planes(planes, dbp, C, C, blocks, s);
+  } else {
+    launch_softmax_xent(bf16_ptr(logits), labels.data_ptr<long>(),
+                        bf16_mut(dl), out.data_ptr<float>(), B, C, dbp,
+                        (float)inv_n, part, ticket, cur_stream());
+  }
   auto loss = out.select(0, 0);
   auto correct = out.select(0, 1);
   return {loss, correct, dl};
@@ -1112,9 +1322,44 @@ void softmax_eval(torch::Tensor logits, torch::Tensor labels,
                       cp, (int)B, (int)C, part, ticket, cur_stream());
 }
 
+void plane_reduce(torch::Tensor planes, torch::Tensor out) {
+  // out[i] += ((p_0[i] + p_1[i]) + ...) + p_{P-1}[i], fp32, planes in index
+  // order; out may be any contiguous 1-D view (16 B alignment not required)
+  CHECK_CUDA(planes); CHECK_F32(planes); CHECK_CONTIG(planes);
+  CHECK_CUDA(out); CHECK_F32(out); CHECK_CONTIG(out);
+  TORCH_CHECK(planes.dim() == 2 && planes.size(0) >= 1,
+              "plane_reduce: planes must be [P >= 1, n]");
+  TORCH_CHECK(out.numel() == planes.size(1),
+              "plane_reduce: out must hold n = planes.size(1) values");
+  TORCH_CHECK(planes.size(0) < (int64_t(1) << 31), "plane_reduce: P too large");
+  TORCH_CHECK(planes.get_device() == out.get_device(),
+              "plane_reduce: planes and out on different devices");
+  if (out.numel() == 0) return;
+  reduce_planes(planes.data_ptr<float>(), out.data_ptr<float>(), out.numel(),
+                planes.size(1), (int)planes.size(0), cur_stream());
+}
+
+std::vector<torch::Tensor> det_workspace() {
+  int dev = -1;
+  hipGetDevice(&dev);
+  std::vector<torch::Tensor> r;
+  for (auto& kv : det_regions())
+    if (std::get<0>(kv.first) == dev) r.push_back(kv.second);
+  return r;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("set_deterministic", [](bool on) { g_deterministic.store(on); },
+        "deterministic mode: gradient ops store per-block planes and reduce "
+        "them in a fixed order; uncovered routes raise", py::arg("on"));
+  m.def("get_deterministic", [] { return det_on(); });
+  m.def("det_workspace", &det_workspace,
+        "plane workspace tensors currently allocated on the current device");
+  m.def("plane_reduce", &plane_reduce,
+        "out[i] += ((p_0[i] + p_1[i]) + ...) + p_{P-1}[i] (fp32, index order)",
+        py::arg("planes"), py::arg("out"));
   m.def("linear_act_fwd", &linear_act_fwd, "fused linear+bias+relu+dropout",
         py::arg("x"), py::arg("w"), py::arg("b"), py::arg("relu"),
         py::arg("p_keep"), py::arg("seed"), py::arg("offset"),

@@ -152,7 +152,11 @@ void conv1_mfma_fwd_kernel(const ushort_t* __restrict__ x,
 // rows w, w+4, ... of each image and one 32x32 fp32 accumulator; waves
 // reduce through LDS and the block flushes 800 + 32 atomics once.
 // ---------------------------------------------------------------------------
-extern "C" __global__ __launch_bounds__(256)
+// DET (deterministic mode): dw is the plane set [blocks][CONV1_DET_PLANE];
+// block b stores its 800 dW sums and 32 db sums into plane b instead of
+// adding into the bucket (db unused).
+template <bool DET>
+__global__ __launch_bounds__(256)
 void conv1_mfma_dw_kernel(const ushort_t* __restrict__ x,
                           const ushort_t* __restrict__ dyp,
                           const uint8_t* __restrict__ am,
@@ -249,6 +253,18 @@ void conv1_mfma_dw_kernel(const ushort_t* __restrict__ x,
   }
   reddb[wave * 2 + h][co] = dbacc;
   __syncthreads();
+  if (DET) {
+    float* pl = dw + (size_t)blockIdx.x * CONV1_DET_PLANE;
+    for (int i = tid; i < 25 * 32; i += 256)
+      pl[i] = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
+    if (tid < 32) {
+      float v = 0.f;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v += reddb[k][tid];
+      pl[25 * 32 + tid] = v;
+    }
+    return;
+  }
   for (int i = tid; i < 25 * 32; i += 256)
     atomicAdd(&dw[i], (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]));
   if (db && tid < 32) {
@@ -292,6 +308,20 @@ void launch_conv1_mfma_dw(const unsigned short* x, const unsigned short* dyp,
   if (NB <= 0) return;
   int G = conv1_mfma_dw_group(NB);
   int blocks = (NB + G - 1) / G;
-  hipLaunchKernelGGL(conv1_mfma_dw_kernel, dim3(blocks), dim3(256), 0, s, x,
-                     dyp, am, dw, db, NB, G);
+  hipLaunchKernelGGL(conv1_mfma_dw_kernel<false>, dim3(blocks), dim3(256), 0,
+                     s, x, dyp, am, dw, db, NB, G);
+}
+
+int conv1_mfma_dw_blocks(int NB) {
+  int G = conv1_mfma_dw_group(NB);
+  return NB <= 0 ? 0 : (NB + G - 1) / G;
+}
+
+void launch_conv1_mfma_dw_det(const unsigned short* x,
+                              const unsigned short* dyp, const uint8_t* am,
+                              float* planes, int NB, hipStream_t s) {
+  if (NB <= 0) return;
+  hipLaunchKernelGGL(conv1_mfma_dw_kernel<true>,
+                     dim3(conv1_mfma_dw_blocks(NB)), dim3(256), 0, s, x, dyp,
+                     am, planes, (float*)nullptr, NB, conv1_mfma_dw_group(NB));
 }

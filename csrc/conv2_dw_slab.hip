@@ -106,7 +106,7 @@ DEV int c2_dswz(int k) { return (((k >> 1) & 1) | (((k >> 3) & 1) << 1)) << 1; }
 
 extern __shared__ __align__(16) ushort_t c2_lds[];
 
-template <int KHB, int NBUF, bool POOLED = false>
+template <int KHB, int NBUF, bool POOLED = false, bool DET = false>
 __global__ __launch_bounds__(256, (KHB == 1 && NBUF == 1) ? 3 : 1)
 void conv2_dw_slab_kernel(const ushort_t* __restrict__ x,
                           const ushort_t* __restrict__ dact,
@@ -308,7 +308,11 @@ void conv2_dw_slab_kernel(const ushort_t* __restrict__ x,
         for (int r = 0; r < 4; ++r) {
           int m = ((kh0 + khl) * 5 + kw) * 32 + wr * 16 + frow + r;
           int n = wc * 32 + ni * 16 + fcol;
-          atomicAdd(dw + m * 64 + n, acc[khl][kw][ni][r]);
+          if (DET)  // deterministic mode: dw is this group's private plane
+            dw[(size_t)grp * CONV2_DET_PLANE + m * 64 + n] =
+                acc[khl][kw][ni][r];
+          else
+            atomicAdd(dw + m * 64 + n, acc[khl][kw][ni][r]);
         }
 }
 
@@ -336,7 +340,7 @@ int conv2_dw_group(int NB) {
   return G < 1 ? 1 : G;
 }
 
-template <int KHB, int NBUF, bool POOLED = false>
+template <int KHB, int NBUF, bool POOLED = false, bool DET = false>
 static void c2_launch(const unsigned short* x, const unsigned short* dact,
                       float* dw, int NB, int G, int blocks, hipStream_t s,
                       const uint8_t* am = nullptr) {
@@ -345,12 +349,12 @@ static void c2_launch(const unsigned short* x, const unsigned short* dact,
     // above 64 KB the dynamic LDS size has to be granted once per kernel
     static const hipError_t granted = hipFuncSetAttribute(
         reinterpret_cast<const void*>(
-            &conv2_dw_slab_kernel<KHB, NBUF, POOLED>),
+            &conv2_dw_slab_kernel<KHB, NBUF, POOLED, DET>),
         hipFuncAttributeMaxDynamicSharedMemorySize, BYTES);
     if (granted != hipSuccess)
       throw std::runtime_error("conv2_dw_slab: LDS size not granted");
   }
-  hipLaunchKernelGGL((conv2_dw_slab_kernel<KHB, NBUF, POOLED>), dim3(blocks),
+  hipLaunchKernelGGL((conv2_dw_slab_kernel<KHB, NBUF, POOLED, DET>), dim3(blocks),
                      dim3(256), BYTES, s, x, dact, dw, NB, G, am);
 }
 
@@ -386,4 +390,29 @@ void launch_conv2_dw_slab_pooled(const unsigned short* x,
   int groups = (NB + G - 1) / G;
   int g8 = (groups + 7) / 8 * 8;
   c2_launch<1, 1, true>(x, gp, dw, NB, G, g8 * 5, s, am);
+}
+
+// deterministic mode: the same kernels storing one plane per image group
+int conv2_dw_groups(int NB) {
+  int G = conv2_dw_group(NB);
+  return NB <= 0 ? 0 : (NB + G - 1) / G;
+}
+
+void launch_conv2_dw_slab_det(const unsigned short* x,
+                              const unsigned short* dact, float* planes,
+                              int NB, hipStream_t s) {
+  if (NB <= 0) return;
+  int g8 = (conv2_dw_groups(NB) + 7) / 8 * 8;
+  c2_launch<1, 1, false, true>(x, dact, planes, NB, conv2_dw_group(NB),
+                               g8 * 5, s);
+}
+
+void launch_conv2_dw_slab_pooled_det(const unsigned short* x,
+                                     const unsigned short* gp,
+                                     const uint8_t* am, float* planes, int NB,
+                                     hipStream_t s) {
+  if (NB <= 0) return;
+  int g8 = (conv2_dw_groups(NB) + 7) / 8 * 8;
+  c2_launch<1, 1, true, true>(x, gp, planes, NB, conv2_dw_group(NB), g8 * 5,
+                              s, am);
 }

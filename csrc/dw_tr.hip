@@ -40,7 +40,7 @@ __device__ __align__(16) unsigned short g_zero_page[8];  // zero-init
 enum { AM_PLAIN = 0, AM_CONV5 = 1 };
 
 template <int BN, int AMODE, int TBM = 128, int TBK = 64, int NBUF = 2,
-          int SW = 0>
+          int SW = 0, int DET = 0>
 __global__ __launch_bounds__(NT) void dw_tr_kernel(GemmParams p) {
   static_assert(TBK % 32 == 0, "TBK in 32-k MFMA halves");
   static_assert(NBUF == 2 || NBUF == 3, "2-buf overlap or 3-buf glds span");
@@ -284,6 +284,27 @@ __global__ __launch_bounds__(NT) void dw_tr_kernel(GemmParams p) {
   // atomics over 16 separate planes (outputs meaningless; isolates the
   // same-address atomic serialization cost in the flush)
   if (p.offset) outp += (size_t)(bz & 15) * p.M * p.ldc;
+  if (DET) {
+    // deterministic mode: k-slice bz stores its tile into its own plane
+    // (every in-range element, zeros included); plane_reduce adds the planes
+    // in slice order and does the single add into the bucket
+    float* pl = p.det_planes + (size_t)bz * p.det_stride;
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi) {
+#pragma unroll
+      for (int ni = 0; ni < NI; ++ni) {
+        int gc = n0 + wc * WN + ni * 16 + fcol;
+        if (gc >= p.N) continue;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          int gr = m0 + wr * WM + mi * 16 + frow + r;
+          if (gr >= p.M) continue;
+          pl[(size_t)gr * p.ldc + gc] = acc[mi][ni][r];
+        }
+      }
+    }
+    return;
+  }
   if (SW) {
     // acc[mi][ni] = D[n = frow + r][m = fcol]: four consecutive n per lane
 #pragma unroll
@@ -359,6 +380,20 @@ static void dw_tr_plain(const GemmParams& p, bool sw, hipStream_t s) {
   else
     hipLaunchKernelGGL((dw_tr_kernel<BN, AM_PLAIN, TBM>), grid, dim3(NT), 0,
                        s, p);
+}
+
+template <int BN, int TBM>
+static void dw_tr_plain_det(const GemmParams& p, hipStream_t s) {
+  dim3 grid(cdiv_h(p.M, TBM) * cdiv_h(p.N, BN) * p.splitk);
+  hipLaunchKernelGGL((dw_tr_kernel<BN, AM_PLAIN, TBM, 64, 2, 0, 1>), grid,
+                     dim3(NT), 0, s, p);
+}
+
+void gemm_dw_tr_det(const GemmParams& p, int tbm, int bn, hipStream_t s) {
+  if (tbm == 64)
+    (bn == 128 ? dw_tr_plain_det<128, 64> : dw_tr_plain_det<64, 64>)(p, s);
+  else
+    (bn == 128 ? dw_tr_plain_det<128, 128> : dw_tr_plain_det<64, 128>)(p, s);
 }
 
 void gemm_dw_tr(const GemmParams& p, int tbm, int bn, bool single_writer,

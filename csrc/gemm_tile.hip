@@ -265,8 +265,11 @@ DEV void writeB(ushort_t (*Bs)[LDK], int tid, const short8 (&regs)[CH]) {
 //   MFMAs so their latency hides under compute, at PIPE=0's LDS footprint
 //   (the dW GEMMs were memory-level-parallelism-bound: ~6 16B loads in
 //   flight per thread serial-blocked at the ds_write vmcnt = ~2 TB/s).
+// DET = 1 (deterministic mode, HAS_DB epilogues): the bias-grad tail reduces
+// in a fixed order and stores this block's column sums into the plane of its
+// block row, p.det_planes + blockIdx.x * p.det_stride (no float atomics).
 template <int BM, int BN, int AMODE, int BMODE, int EPI, int OUT, int PIPE,
-          int SWZ = 0>
+          int SWZ = 0, int DET = 0>
 __global__ __launch_bounds__(NTHREADS)
 void gemm_tile_kernel(GemmParams p) {
   constexpr int WM = BM / 2, WN = BN / 2;
@@ -285,8 +288,8 @@ void gemm_tile_kernel(GemmParams p) {
   // EPI_UNPOOL / EPI_MASK_DB: per-column bias-grad partials, flushed once
   constexpr bool HAS_DB = (EPI == EPI_UNPOOL || EPI == EPI_MASK_DB ||
                            EPI == EPI_POOLMASK_DB);
-  __shared__ float dbred[HAS_DB ? BN : 1];
-  if (HAS_DB && threadIdx.x < BN) dbred[threadIdx.x] = 0.f;
+  __shared__ float dbred[HAS_DB ? (DET ? 2 * BN : BN) : 1];
+  if (HAS_DB && !DET && threadIdx.x < BN) dbred[threadIdx.x] = 0.f;
 
   const int tid = threadIdx.x;
   // EPI_UNPOOL line-store path (host sets p.unpool_lines when Cout % 64 ==
@@ -777,7 +780,28 @@ epilogue:
       }
     }
   }
-  if (HAS_DB) {
+  if (HAS_DB && DET) {
+    // fixed-order tail: a column's eight partials (2 wave rows x 4 row groups
+    // of 16 lanes) are added row group 0..3 by shuffles, parked one LDS row
+    // per wave row, then added wave row 0 + 1.  Every in-range column is
+    // stored, zeros included, so the plane never holds stale values.
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni) {
+      float v = dbloc[ni];
+      float s = __shfl(v, fcol, 64);
+      s += __shfl(v, fcol + 16, 64);
+      s += __shfl(v, fcol + 32, 64);
+      s += __shfl(v, fcol + 48, 64);
+      if (lane < 16) dbred[wr * BN + wc * WN + ni * 16 + fcol] = s;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < BN) {
+      int gc = n0 + (int)threadIdx.x;
+      if (gc < p.N)
+        p.det_planes[(size_t)blockIdx.x * p.det_stride + gc] =
+            dbred[threadIdx.x] + dbred[BN + threadIdx.x];
+    }
+  } else if (HAS_DB) {
     // bias-grad flush: lane partials -> LDS per-column -> one global
     // atomicAdd per block column (UNPOOL: channel = col % Cout)
 #pragma unroll
@@ -812,6 +836,14 @@ static inline int cdiv_host(int a, int b) { return (a + b - 1) / b; }
   void name(const GemmParams& p, hipStream_t s) {                            \
     dim3 grid(cdiv_host(p.M, BM) * cdiv_host(p.N, BN) * p.splitk);           \
     hipLaunchKernelGGL((gemm_tile_kernel<BM, BN, AM, BMo, EPI, OUT, PIPE,    \
+                                         1>),                                \
+                       grid, dim3(NTHREADS), 0, s, p);                       \
+  }
+
+#define GEMM_ENTRY_DET(name, BM, BN, AM, BMo, EPI, OUT, PIPE)               \
+  void name(const GemmParams& p, hipStream_t s) {                            \
+    dim3 grid(cdiv_host(p.M, BM), cdiv_host(p.N, BN), p.splitk);             \
+    hipLaunchKernelGGL((gemm_tile_kernel<BM, BN, AM, BMo, EPI, OUT, PIPE, 0, \
                                          1>),                                \
                        grid, dim3(NTHREADS), 0, s, p);                       \
   }
@@ -860,3 +892,12 @@ GEMM_ENTRY(conv_dx_gemm, 128, 32, A_CONV_DX, B_CONV_DX_W, EPI_NONE, OUT_BF16, 0)
 GEMM_ENTRY_SWZ(conv_dw_gemm, 128, 64, A_CONV_DW, B_KMAJ, EPI_NONE, OUT_F32_ATOMIC, 2)
 // conv1 dW: M=25 -> 32x32 tile (78% M-utilization vs 39% at BM=64)
 GEMM_ENTRY_SWZ(conv1_dw_gemm, 32, 32, A_CONV_DW, B_KMAJ, EPI_NONE, OUT_F32_ATOMIC, 2)
+// deterministic mode: the two bias tails with the fixed-order plane flush, and
+// the scatter-staged dW (fc2: N = 10 is off the tr16 route) with one stored
+// plane per k-slice instead of atomics
+GEMM_ENTRY_DET(gemm_dx_poolmask_128_det, 128, 128, A_N, B_NMAJ, EPI_POOLMASK_DB, OUT_BF16, 1)
+GEMM_ENTRY_DET(gemm_dx_poolmask_64_det, 64, 64, A_N, B_NMAJ, EPI_POOLMASK_DB, OUT_BF16, 1)
+GEMM_ENTRY_DET(gemm_dx_mask_128_det, 128, 128, A_N, B_NMAJ, EPI_MASK_DB, OUT_BF16, 1)
+GEMM_ENTRY_DET(gemm_dx_mask_64_det, 64, 64, A_N, B_NMAJ, EPI_MASK_DB, OUT_BF16, 1)
+GEMM_ENTRY_SWZ(gemm_dw_planes_128, 128, 128, A_T, B_KMAJ, EPI_NONE, OUT_F32_SLICES, 2)
+GEMM_ENTRY_SWZ(gemm_dw_planes_64, 64, 64, A_T, B_KMAJ, EPI_NONE, OUT_F32_SLICES, 2)

@@ -25,6 +25,13 @@ struct GemmParams {
                       // of a tile sums the planes and writes bf16 y (p.Y)
   unsigned short* Y;  // OUT_F32_SLICES_FIX: final bf16 output [M][N]
   int relu;           // OUT_F32_SLICES_FIX: relu in the fix-up
+  // deterministic mode (det_reduce.hip): the *_det entries store the block's
+  // contribution into its private plane instead of adding into C / db.
+  // dw_tr: plane = k-slice, [M][ldc] floats at det_planes + slice*det_stride.
+  // GEMM bias tails: plane = block row, [N] floats at det_planes +
+  // blockIdx.x * det_stride.
+  float* det_planes;
+  long det_stride;
 };
 
 // gemm_tile.hip — implicit-GEMM MFMA entry points
@@ -55,6 +62,9 @@ void conv_dw_tr(const GemmParams&, hipStream_t);    // 5x5-SAME gather A
 // one lane, no atomics
 void gemm_dw_tr(const GemmParams&, int tbm, int bn, bool single_writer,
                 hipStream_t);
+// the same split over k-slices, each slice storing its own plane
+// (p.det_planes / p.det_stride); p.C is not touched
+void gemm_dw_tr_det(const GemmParams&, int tbm, int bn, hipStream_t);
 
 // ops_misc.hip — host wrappers
 void launch_relu_drop_bwd(const unsigned short* dy, const unsigned short* y,
@@ -71,6 +81,14 @@ void launch_softmax_xent(const unsigned short* logits, const long* labels,
                          unsigned short* dlogits, float* out, int B, int C,
                          float* db, float inv_n, float* part,
                          unsigned* ticket, hipStream_t);
+int softmax_xent_blocks(int B);  // grid of the launch above
+// deterministic form: `dbplanes` [softmax_xent_blocks(B)][C] receives every
+// block's column sums by plain stores (fixed in-block order); db is not
+// touched
+void launch_softmax_xent_det(const unsigned short* logits, const long* labels,
+                             unsigned short* dlogits, float* out, int B, int C,
+                             float* dbplanes, float inv_n, float* part,
+                             unsigned* ticket, hipStream_t);
 void launch_sgd_step(float* master, float* grad, unsigned short* shadow,
                      int has_shadow, long n, float lr_scale, float dc_keep,
                      uint64_t seed, uint64_t offset, float* momentum, float mu,
@@ -171,6 +189,33 @@ void launch_conv1_direct_fwd(const unsigned short* x, const unsigned short* w,
                              const float* bias, unsigned short* y,
                              uint8_t* amax, int NB, int H, int W, int Cout,
                              hipStream_t);
+// gemm_tile.hip — deterministic-mode entries.  The bias tails reduce in a
+// fixed in-block order and store one [N] plane per block row (p.det_planes);
+// the scatter-staged dW stores one [M][ldc] plane per k-slice at p.C
+void gemm_dx_poolmask_128_det(const GemmParams&, hipStream_t);
+void gemm_dx_poolmask_64_det(const GemmParams&, hipStream_t);
+void gemm_dx_mask_128_det(const GemmParams&, hipStream_t);
+void gemm_dx_mask_64_det(const GemmParams&, hipStream_t);
+void gemm_dw_planes_128(const GemmParams&, hipStream_t);
+void gemm_dw_planes_64(const GemmParams&, hipStream_t);
+// det_reduce.hip — out[i] += ((p_0[i] + p_1[i]) + ...) + p_{P-1}[i], planes
+// in index order, for up to PLANE_REDUCE_MAX destinations in one launch
+#define PLANE_REDUCE_MAX 4
+struct PlaneReduceDesc {
+  const float* planes;  // plane p starts at planes + p * stride
+  float* out;
+  long n, stride;
+  int P;
+  int store;  // 1: out = S (an intermediate of a two-stage sum), 0: out += S
+  int head;   // filled by the launcher: scalar elements before the 16 B body
+  long nvec;  // filled by the launcher: 16 B groups in the body
+};
+struct PlaneReduceArgs {
+  PlaneReduceDesc d[PLANE_REDUCE_MAX];
+  int block0[PLANE_REDUCE_MAX];
+  int n;
+};
+void launch_plane_reduce(const PlaneReduceDesc* descs, int n, hipStream_t);
 // B-transposed (pre-transposed weight) forward GEMM entries
 void gemm_fwd_bias_128_bt(const GemmParams&, hipStream_t);
 void gemm_fwd_bias_64_bt(const GemmParams&, hipStream_t);
@@ -217,6 +262,13 @@ void launch_conv1_mfma_fwd(const unsigned short* x, const unsigned short* w,
 void launch_conv1_mfma_dw(const unsigned short* x, const unsigned short* dyp,
                           const uint8_t* am, float* dw, float* db, int NB,
                           hipStream_t);
+// deterministic form: block b stores its 800 dW + 32 db sums into
+// planes[b][0..832); returns the block (= plane) count
+#define CONV1_DET_PLANE 832
+int conv1_mfma_dw_blocks(int NB);
+void launch_conv1_mfma_dw_det(const unsigned short* x,
+                              const unsigned short* dyp, const uint8_t* am,
+                              float* planes, int NB, hipStream_t);
 // conv2_dw_slab.hip — LeNet conv2 dW (14x14, Cin=32, Cout=64) from pixel-
 // major per-image LDS slabs (glds + tr16); DMNIST_DW2_SLAB=0 (read per call)
 // routes the shape back to conv_dw_tr
@@ -229,6 +281,19 @@ void launch_conv2_dw_slab(const unsigned short* x, const unsigned short* dact,
 void launch_conv2_dw_slab_pooled(const unsigned short* x,
                                  const unsigned short* gp, const uint8_t* am,
                                  float* dw, int NB, hipStream_t);
+// deterministic forms of the two launchers: image group g stores its 51 200
+// sums into planes[g][..] (its five kernel-row blocks write disjoint rows).
+// Only the conv2_dw_groups(NB) real groups write; the blocks that pad the
+// grid to a multiple of 8 groups write nothing and their planes are not read.
+#define CONV2_DET_PLANE (25 * 32 * 64)
+int conv2_dw_groups(int NB);
+void launch_conv2_dw_slab_det(const unsigned short* x,
+                              const unsigned short* dact, float* planes,
+                              int NB, hipStream_t);
+void launch_conv2_dw_slab_pooled_det(const unsigned short* x,
+                                     const unsigned short* gp,
+                                     const uint8_t* am, float* planes, int NB,
+                                     hipStream_t);
 // gemm_tile.hip — split-K fwd slice entries + their summing epilogue
 void gemm_fwd_slices_64(const GemmParams&, hipStream_t);
 void gemm_fwd_slices_64_bt(const GemmParams&, hipStream_t);

@@ -136,7 +136,11 @@ void pool_bwd_scatter_kernel(const ushort_t* dy, const ushort_t* y,
 // are one persistent workspace per device, so launches on one device must
 // not overlap (they never do: one softmax per training step).
 // ---------------------------------------------------------------------------
-template <int CC>
+// DET (deterministic mode): db is the plane set [gridDim.x][C]; the wave sums
+// (a fixed shuffle tree) are parked one LDS row per wave, added in wave order
+// and STORED into this block's plane; plane_reduce adds the planes in block
+// order.  No float atomics, no skipped zeros.
+template <int CC, bool DET = false>
 __global__ __launch_bounds__(256)
 void softmax_xent_t_kernel(const ushort_t* logits, const long* labels,
                            ushort_t* dlogits, float* out, int B, int C,
@@ -151,8 +155,8 @@ void softmax_xent_t_kernel(const ushort_t* logits, const long* labels,
   // inv_n: out[1] += correct * inv_n (1/B = accuracy mean in-kernel).
   if (CC) C = CC;
   __shared__ float wred[4][2];  // per-wave (loss, correct) partials
-  __shared__ float dbred[16];
-  if (db && threadIdx.x < 16) dbred[threadIdx.x] = 0.f;
+  __shared__ float dbred[DET ? 64 : 16];
+  if (!DET && db && threadIdx.x < 16) dbred[threadIdx.x] = 0.f;
   __syncthreads();
   int b = blockIdx.x * blockDim.x + threadIdx.x;
   float loss = 0.f, correct = 0.f;
@@ -240,12 +244,22 @@ void softmax_xent_t_kernel(const ushort_t* logits, const long* labels,
 #pragma unroll
       for (int off = 32; off > 0; off >>= 1)
         dsum += __shfl_down(dsum, off, 64);
-      if ((threadIdx.x & 63) == 0 && dsum != 0.f)
+      if (DET) {
+        if ((threadIdx.x & 63) == 0) dbred[(threadIdx.x >> 6) * 16 + c] = dsum;
+      } else if ((threadIdx.x & 63) == 0 && dsum != 0.f) {
         atomicAdd(&dbred[c], dsum);
+      }
     }
   }
   __syncthreads();
-  if (db && (int)threadIdx.x < C) {
+  if (DET) {
+    if (db && (int)threadIdx.x < C) {
+      float v2 = dbred[threadIdx.x];
+      for (unsigned wv = 1; wv < (blockDim.x + 63) / 64; ++wv)
+        v2 += dbred[wv * 16 + threadIdx.x];
+      db[(size_t)blockIdx.x * C + threadIdx.x] = v2;
+    }
+  } else if (db && (int)threadIdx.x < C) {
     float v2 = dbred[threadIdx.x];
     if (v2 != 0.f) atomicAdd(&db[threadIdx.x], v2);
   }
@@ -500,6 +514,32 @@ void launch_pool_bwd_scatter(const unsigned short* dy, const unsigned short* y,
                                  : pool_bwd_gather_kernel,
                      dim3(blocks), dim3(256), 0, s, dy, y, amax, dact, db,
                      Mpool, C, H, W, Wo);
+}
+
+static int softmax_xent_bt(int B) {
+  int bt = B >= 2048 ? 256 : 64;
+  if (cdivh(B, bt) > SOFTMAX_MAX_BLOCKS) bt = 256;
+  return bt;
+}
+
+int softmax_xent_blocks(int B) { return cdivh(B, softmax_xent_bt(B)); }
+
+// deterministic mode: same grid, db column sums stored per block into
+// dbplanes [blocks][C]
+void launch_softmax_xent_det(const unsigned short* logits, const long* labels,
+                             unsigned short* dlogits, float* out, int B, int C,
+                             float* dbplanes, float inv_n, float* part,
+                             unsigned* ticket, hipStream_t s) {
+  int bt = softmax_xent_bt(B);
+  dim3 grid(cdivh(B, bt));
+  if (C == 10)
+    hipLaunchKernelGGL((softmax_xent_t_kernel<10, true>), grid, dim3(bt), 0, s,
+                       logits, labels, dlogits, out, B, C, dbplanes, inv_n,
+                       part, ticket);
+  else
+    hipLaunchKernelGGL((softmax_xent_t_kernel<0, true>), grid, dim3(bt), 0, s,
+                       logits, labels, dlogits, out, B, C, dbplanes, inv_n,
+                       part, ticket);
 }
 
 void launch_softmax_xent(const unsigned short* logits, const long* labels,

@@ -26,6 +26,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from .. import _C
 from ..data import DeviceDataSet, SyntheticDataSet
 from ..models import build_model
 from ..ops import functional as Fx
@@ -74,6 +75,46 @@ def lr_at(step: int, flags, num_examples: int, num_replicas: int) -> float:
             flags.learning_rate_decay_factor ** (step // decay_steps))
 
 
+def check_deterministic(flags, device, compute_dtype, world) -> None:
+    """--deterministic: raise on every setting that cannot be reproducible
+    (never a silent fallback).  The three timing-driven sync modes conflict
+    on any device; on a GPU the mode covers the fused bf16 LeNet step on its
+    default backward route only."""
+    def conflict(what, why):
+        raise ValueError(f"--deterministic cannot be combined with {what}: "
+                         f"{why}")
+    if flags.interval_method:
+        conflict("--interval_method",
+                 "wall-clock aggregation depends on timing by design")
+    if 0 < flags.num_replicas_to_aggregate < world:
+        conflict("--num_replicas_to_aggregate below the world size",
+                 "which gradients are aggregated depends on arrival order")
+    if (flags.straggler_timeout_ms or 0) > 0:
+        conflict("--straggler_timeout_ms > 0",
+                 "dropping a gradient depends on the measured compute time")
+    if device.type != "cuda":
+        return
+    if flags.model != "lenet":
+        conflict(f"--model {flags.model}",
+                 "only the fused LeNet step has a deterministic backward")
+    if compute_dtype != torch.bfloat16:
+        conflict("--compute_dtype fp32",
+                 "the deterministic kernels are the bf16 HIP path")
+    if getattr(flags, "fused_step", "auto") == "off":
+        conflict("--fused_step off",
+                 "the autograd composites use float atomics")
+    for env, bad, why in (
+            ("DMNIST_POOL2_FUSED", "0", "the dX+unpool route uses atomics"),
+            ("DMNIST_CONV1_VALU", "1", "the VALU conv1 dW flushes with "
+                                       "float atomics"),
+            ("DMNIST_EAGER_FUSED", "0", "the autograd composites use float "
+                                        "atomics")):
+        v = os.environ.get(env)
+        if v is not None and ((bad == "0" and v == "0")
+                              or (bad == "1" and v not in ("", "0"))):
+            conflict(f"{env}={v}", why)
+
+
 class Trainer:
     """Owns model + flat buffers + sync engine; one step() per iteration."""
 
@@ -87,6 +128,14 @@ class Trainer:
             self.compute_dtype = torch.bfloat16 if self.device.type == "cuda" else torch.float32
         else:
             self.compute_dtype = dict(fp32=torch.float32, bf16=torch.bfloat16)[flags.compute_dtype]
+        # --deterministic: refuse what cannot be reproducible, then flip the
+        # kernel library's per-process switch (GPU HIP path only; CPU
+        # training is bitwise deterministic as it is)
+        self.deterministic = bool(getattr(flags, "deterministic", False))
+        if self.deterministic:
+            check_deterministic(flags, self.device, self.compute_dtype, world)
+        if self.device.type == "cuda" and _C.has_ext():
+            _C.ext().set_deterministic(self.deterministic)
         self.model = build_model(flags.model, seed=flags.seed,
                                  compute_dtype=self.compute_dtype).to(self.device)
         self.fp = FlatParams(self.model, device=self.device,

@@ -452,3 +452,19 @@ def softmax_eval(logits, labels, loss_sum, counts, pred=None,
         pred.copy_(torch.where(live, p, torch.full_like(p, 255)).to(pred.dtype))
     if cursor_dev is not None:
         cursor_dev += B
+
+
+def plane_reduce(planes, out):
+    """The deterministic mode's ordered reduction, in place:
+    S = ((p_0 + p_1) + p_2) + ... + p_{P-1} (fp32, planes in index order,
+    starting from p_0), then out += S (one fp32 add).  A sequential loop over
+    the planes; each step is one elementwise fp32 add, so no reassociation."""
+    assert planes.dim() == 2 and planes.shape[0] >= 1
+    assert planes.dtype == torch.float32 and out.dtype == torch.float32
+    assert out.numel() == planes.shape[1]
+    p = planes.detach().cpu()
+    s = p[0].clone()
+    for i in range(1, p.shape[0]):
+        s = s + p[i]
+    out += s.to(out.device).view_as(out)
+    return out

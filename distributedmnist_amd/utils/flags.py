@@ -134,6 +134,14 @@ def build_train_parser() -> argparse.ArgumentParser:
                         "num_updates), updated inside the SGD kernel, saved "
                         "in the checkpoint as flat_ema and used by "
                         "--eval_every_steps; 0 = off")
+    p.add_argument("--deterministic", action="store_true",
+                   help="bitwise-reproducible gradients on the GPU: the fused "
+                        "LeNet step reduces every weight and bias gradient "
+                        "in a fixed order (per-block planes + an ordered "
+                        "reduction) instead of fp32 atomics; routes that are "
+                        "not covered raise. Not with --interval_method, "
+                        "--num_replicas_to_aggregate below the world size or "
+                        "--straggler_timeout_ms; accepted and a no-op on CPU")
     return p
 
 
