@@ -970,6 +970,17 @@ void conv_dw_pooled_into(torch::Tensor x, torch::Tensor gp, torch::Tensor am,
 }
 
 // --------------------------------------------------------------------------
+// Per-device workspace of the softmax last-block reduction: two partials per
+// block + the self-resetting ticket behind them.  softmax_xent_fwd and
+// fc2_head share it: a step runs one or the other, ordered on its stream.
+float* softmax_workspace(const torch::Tensor& like, hipStream_t s) {
+  static auto* ws = new WorkspaceSlots(64);
+  return device_workspace(
+      *ws, like, 2 * SOFTMAX_MAX_BLOCKS + 1, at::kFloat, s, "softmax_xent",
+      "softmax_xent_fwd / fc2_head: first call on a device allocates its "
+      "workspace and must run outside graph capture").data_ptr<float>();
+}
+
 std::vector<torch::Tensor> softmax_xent_fwd(torch::Tensor logits,
                                             torch::Tensor labels,
                                             c10::optional<torch::Tensor> db_out,
@@ -989,12 +1000,7 @@ std::vector<torch::Tensor> softmax_xent_fwd(torch::Tensor logits,
   // launch per step.  Its workspace (per-block partials + ticket counter)
   // is allocated and zeroed once per device; the counter resets itself.
   auto out = torch::empty({2}, logits.options().dtype(at::kFloat));
-  static auto* ws = new WorkspaceSlots(64);
-  float* part = device_workspace(
-      *ws, logits, 2 * SOFTMAX_MAX_BLOCKS + 1, at::kFloat, cur_stream(),
-      "softmax_xent",
-      "softmax_xent_fwd: first call on a device allocates its "
-      "workspace and must run outside graph capture").data_ptr<float>();
+  float* part = softmax_workspace(logits, cur_stream());
   unsigned* ticket = reinterpret_cast<unsigned*>(part + 2 * SOFTMAX_MAX_BLOCKS);
   float* dbp = nullptr;
   if (db_out.has_value() && db_out->defined())
@@ -1017,6 +1023,86 @@ std::vector<torch::Tensor> softmax_xent_fwd(torch::Tensor logits,
   auto loss = out.select(0, 0);
   auto correct = out.select(0, 1);
   return {loss, correct, dl};
+}
+
+// Rows per block of the fused fc2 head, by batch size (solo sweep,
+// profiles/fc2_head_b1024_b8192.md); DMNIST_FC2_R=16|32|64 (read per call)
+// forces one.
+int fc2_head_rows(int B) {
+  if (const char* e = getenv("DMNIST_FC2_R")) {
+    int r = atoi(e);
+    if (r == 16 || r == 32 || r == 64) return r;
+  }
+  // 64 rows per block from B = 256 up (fewest dW2 / db1 flushes: the kernel's
+  // cost above B = 1024 is its fp32 atomics, 5632 per block); at B = 64 two
+  // blocks of 32 beat one of 64.  The edge sits between the measured sizes.
+  return B < 160 ? 32 : 64;
+}
+
+// The 512 -> 10 layer of the training step: fc2 forward, softmax-xent (+db2),
+// fc2 dW and fc2 dX with the fc1 mask (+db1).  Returns (loss, acc, dyeff1);
+// dw2_out / db2_out / db1_out are accumulated into.  THE route decision of
+// this layer: one fc2_head_kernel launch, or the four separate steps when
+// DMNIST_FC2_FUSED=0 (read per call), in deterministic mode (its planes route
+// stays as it is) and for every shape or alignment the kernel does not cover.
+std::vector<torch::Tensor> fc2_head(torch::Tensor a1, torch::Tensor w2,
+                                    torch::Tensor w2T, torch::Tensor b2,
+                                    torch::Tensor labels,
+                                    torch::Tensor dw2_out,
+                                    torch::Tensor db2_out,
+                                    torch::Tensor db1_out, double p_keep,
+                                    double inv_n) {
+  CHECK_CUDA(a1); CHECK_BF16(a1); CHECK_CONTIG(a1);
+  CHECK_BF16(w2); CHECK_CONTIG(w2);
+  CHECK_BF16(w2T); CHECK_CONTIG(w2T);
+  CHECK_F32(b2); CHECK_CONTIG(b2);
+  TORCH_CHECK(labels.scalar_type() == at::kLong, "labels must be int64");
+  CHECK_CONTIG(labels);
+  CHECK_F32(dw2_out); CHECK_CONTIG(dw2_out);
+  CHECK_F32(db2_out); CHECK_CONTIG(db2_out);
+  CHECK_F32(db1_out); CHECK_CONTIG(db1_out);
+  TORCH_CHECK(a1.dim() == 2 && w2.dim() == 2 && w2T.dim() == 2,
+              "fc2_head: a1, w2 and w2T are 2-D");
+  const int64_t B = a1.size(0), K = a1.size(1), C = w2.size(1);
+  TORCH_CHECK(w2.size(0) == K, "fc2_head: w2 is [K][C]");
+  TORCH_CHECK(w2T.size(0) == C && w2T.size(1) == K, "fc2_head: w2T is [C][K]");
+  TORCH_CHECK(b2.numel() == C && db2_out.numel() == C,
+              "fc2_head: b2 and db2_out hold C values");
+  TORCH_CHECK(dw2_out.numel() == K * C, "fc2_head: dw2_out holds K*C values");
+  TORCH_CHECK(db1_out.numel() == K, "fc2_head: db1_out holds K values");
+  TORCH_CHECK(labels.numel() == B, "fc2_head: one label per row");
+  TORCH_CHECK(p_keep > 0.0 && p_keep <= 1.0, "fc2_head: p_keep in (0, 1]");
+  TORCH_CHECK(B <= 256 * SOFTMAX_MAX_BLOCKS, "fc2_head: batch too large");
+  auto s = cur_stream();
+
+  const char* fe = getenv("DMNIST_FC2_FUSED");
+  const int R = fc2_head_rows((int)B);
+  const bool fused =
+      !(fe && atoi(fe) == 0) && !det_on() && B > 0 && C == 10 &&
+      K == FC2_HEAD_K &&
+      fc2_head_blocks((int)B, R) <= SOFTMAX_MAX_BLOCKS &&
+      ((uintptr_t)a1.data_ptr() & 15) == 0 &&
+      ((uintptr_t)w2T.data_ptr() & 15) == 0;
+  if (!fused) {
+    auto logits = linear_act_fwd_impl(a1, w2, b2, false, 1.0, 0, 0, nullptr,
+                                      w2T);
+    auto sm = softmax_xent_fwd(logits, labels, db2_out, inv_n);
+    linear_dw_step(a1, sm[2], dw2_out.data_ptr(), s);
+    auto dyeff1 = linear_dx_mask(sm[2], w2, a1, db1_out, p_keep);
+    return {sm[0], sm[1], dyeff1};
+  }
+  auto dyeff1 = torch::empty_like(a1);
+  TORCH_CHECK(((uintptr_t)dyeff1.data_ptr() & 15) == 0,
+              "fc2_head: dyeff1 must be 16-byte aligned");
+  auto out = torch::empty({2}, a1.options().dtype(at::kFloat));
+  float* part = softmax_workspace(a1, s);
+  unsigned* ticket = reinterpret_cast<unsigned*>(part + 2 * SOFTMAX_MAX_BLOCKS);
+  launch_fc2_head(R, bf16_ptr(a1), bf16_ptr(w2T), b2.data_ptr<float>(),
+                  labels.data_ptr<long>(), bf16_mut(dyeff1),
+                  dw2_out.data_ptr<float>(), db2_out.data_ptr<float>(),
+                  db1_out.data_ptr<float>(), out.data_ptr<float>(), (int)B,
+                  (float)(1.0 / p_keep), (float)inv_n, part, ticket, s);
+  return {out.select(0, 0), out.select(0, 1), dyeff1};
 }
 
 // optional moving-average buffer of the SGD pass: nullptr = off
@@ -1424,6 +1510,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("softmax_xent_fwd", &softmax_xent_fwd, "fused softmax-CE (+grad, +optional fc2 db, +optional acc-mean scale)",
         py::arg("logits"), py::arg("labels"),
         py::arg("db_out") = c10::nullopt, py::arg("inv_n") = 1.0);
+  m.def("fc2_head", &fc2_head,
+        "fc2 forward + softmax-xent (+db2) + fc2 dW + fc2 dX with the fc1 "
+        "mask (+db1): one launch, or the four separate steps; returns "
+        "(loss, acc, dyeff1)",
+        py::arg("a1"), py::arg("w2"), py::arg("w2T"), py::arg("b2"),
+        py::arg("labels"), py::arg("dw2_out"), py::arg("db2_out"),
+        py::arg("db1_out"), py::arg("p_keep"), py::arg("inv_n") = 1.0);
+  m.def("fc2_head_rows", [](int64_t B) { return fc2_head_rows((int)B); },
+        "rows per block the fused fc2 head picks at batch size B");
   m.def("sgd_step", &sgd_step, "fused flat SGD(+momentum) apply",
         py::arg("master"), py::arg("grad"), py::arg("shadow"),
         py::arg("has_shadow"), py::arg("lr"), py::arg("scale"),

@@ -89,6 +89,20 @@ void launch_softmax_xent_det(const unsigned short* logits, const long* labels,
                              unsigned short* dlogits, float* out, int B, int C,
                              float* dbplanes, float inv_n, float* part,
                              unsigned* ticket, hipStream_t);
+// fc2_head.hip — fc2 forward + softmax-xent + fc2 dX/mask/db1 + fc2 dW in one
+// launch for the LeNet shape (K == FC2_HEAD_K features, 10 classes); R in
+// {16, 32, 64} rows per block.  a1, w2T and dyeff must be 16 B aligned.  out
+// and part/ticket as launch_softmax_xent (the same workspace: the grid,
+// fc2_head_blocks(B, R), must not exceed SOFTMAX_MAX_BLOCKS); dw2 [K][10],
+// db2 [10] and db1 [K] are accumulated into; inv_keep = 1 / p_keep.
+#define FC2_HEAD_K 512
+int fc2_head_blocks(int B, int R);
+void launch_fc2_head(int R, const unsigned short* a1,
+                     const unsigned short* w2T, const float* b2,
+                     const long* labels, unsigned short* dyeff, float* dw2,
+                     float* db2, float* db1, float* out, int B,
+                     float inv_keep, float inv_n, float* part,
+                     unsigned* ticket, hipStream_t);
 void launch_sgd_step(float* master, float* grad, unsigned short* shadow,
                      int has_shadow, long n, float lr_scale, float dc_keep,
                      uint64_t seed, uint64_t offset, float* momentum, float mu,

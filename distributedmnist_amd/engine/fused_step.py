@@ -6,8 +6,9 @@ the hipGraph capture (graphstep.py).
 Backward dataflow (both pool backwards fused into their consumers: neither
 pre-pool gradient, dact1 or dact2, is ever written to memory):
 
-  softmax(+db2) -> dl --> dW2
-     dl --> dx2+mask+db1 = dyeff1 --> dW1
+  a1 --> fc2 head: logits, softmax(+db2), dW2, dx2+mask+db1 = dyeff1
+           (one kernel; logits and dlogits stay in LDS)
+              dyeff1 --> dW1
               dyeff1 --> dX+poolmask = gp2 [B,7,7,64] (+db_conv2)
                 (gp2, am2) --> conv2 dW   (dact2 rebuilt in the LDS slab)
                 (gp2, am2) --> conv2 dX = dxc --> conv1 dW+db (pooled)
@@ -132,7 +133,7 @@ class FusedLeNetStep:
         return s0, (s0 if self.single_stream else self.side)
 
     def _fc_part(self, x, labels, step_dev, reduce_fc):
-        """Forward, softmax, fc2 dW, fc2 dX+mask, fc1 dW, fc1 dX+poolmask.
+        """Forward, the fc2 head, fc1 dW, fc1 dX+poolmask.
         reduce_fc issues the fc-slice all-reduce on s1 right after fc1 dW.
         Returns (loss, acc, _conv_part's arguments, keep): keep holds every
         tensor a side-stream op of either part reads, and the caller stores
@@ -151,29 +152,22 @@ class FusedLeNetStep:
         a1 = ext.linear_act_fwd_dev(h2, sh["fc1_w"], m.fc1_b, True,
                                     self.p_keep, self.seed, step_dev,
                                     shT["fc1_w"])
-        logits = ext.linear_act_fwd(a1, sh["fc2_w"], m.fc2_b, False, 1.0,
-                                    0, 0, shT["fc2_w"])
-        # softmax computes the fc2 bias grad in the same pass (column sums
-        # of dlogits) — no standalone mask_db launch for fc2
-        # inv_n folds the accuracy mean into the kernel: no scalar-divide
-        # launch per step; `acc` below is already the MEAN accuracy
-        loss, acc, dl = ext.softmax_xent_fwd(logits, labels,
-                                             db_out=gv("fc2_b"),
-                                             inv_n=1.0 / B)
+        # the whole fc2 layer in one op (s0): forward, softmax (+ fc2 bias
+        # grad, loss, MEAN accuracy via inv_n), fc2 dW, and fc2 dX with the
+        # fc1 relu+dropout mask (+ fc1 bias grad).  One kernel by default;
+        # the op itself falls back to the four separate launches
+        # (DMNIST_FC2_FUSED=0, deterministic mode, uncovered shapes)
+        loss, acc, dyeff1 = ext.fc2_head(a1, sh["fc2_w"], shT["fc2_w"],
+                                         m.fc2_b, labels, gv("fc2_w"),
+                                         gv("fc2_b"), gv("fc1_b"),
+                                         self.p_keep, 1.0 / B)
 
         # ---- backward: dX chain on s0, dW GEMMs on s1 ----
         self._fork(s1, s0)
         with torch.cuda.stream(s1):
-            ext.linear_dw_into(a1, dl, gv("fc2_w"))
-        # fc2 dX with the fc1 relu+dropout mask folded into the epilogue
-        # (+ fc1 bias grad) — replaces linear_dx + mask_db
-        dyeff1 = ext.linear_dx_mask(dl, sh["fc2_w"], a1, gv("fc1_b"),
-                                    self.p_keep)
-        self._fork(s1, s0)
-        with torch.cuda.stream(s1):
             ext.linear_dw_into(h2, dyeff1, gv("fc1_w"))
             if reduce_fc:
-                # every fc gradient (fc2 via the earlier s1 work + the db's
+                # every fc gradient (fc2's and the db's from the head on s0,
                 # ordered by wait_stream) is final here
                 self.t.engine.wire_allreduce(self.fc_slice,
                                              start=self.fc_offset)
@@ -182,7 +176,7 @@ class FusedLeNetStep:
         # itself happens in the conv2 dW / dX slab staging.  conv2_b is in
         # the conv slice, reduced after the conv part in either form.
         g2 = self._fc1_dx(dyeff1, am2)
-        keep = (a1, h2, dyeff1, dl, y1, g2, am2)
+        keep = (a1, h2, dyeff1, y1, g2, am2)
         return loss, acc, (x, y1, am1, g2, am2), keep
 
     def _conv_part(self, x, y1, am1, g2, am2):

@@ -154,6 +154,36 @@ def softmax_xent_fwd(logits, labels):
     return loss, correct, dl
 
 
+def fc2_head(a1, w2, b2, labels, p_keep: float):
+    """The fc2 layer of the training step in one piece: forward, softmax
+    cross-entropy, fc2 dW and fc2 dX with the fc1 relu/dropout mask.
+
+    a1: [B,K] post-relu/dropout activation, w2: [K,C], b2: [C], labels: [B].
+    fp64 arithmetic with the GPU route's rounding points: the logits and
+    dlogits are rounded to a1.dtype, db2 sums the unrounded dlogits, the mask
+    is a1 > 0 and kept gradients are scaled by 1/p_keep.
+
+    Returns (loss, correct, dyeff1 [B,K] in a1.dtype, dw2 [K,C], db1 [K],
+    db2 [C]); the scalars and the three sums are fp64.
+    """
+    B = a1.shape[0]
+    af, wf = a1.double(), w2.double()
+    logits = (af @ wf + b2.double()).to(a1.dtype).double()
+    z = logits - logits.max(dim=1, keepdim=True).values
+    ez = z.exp()
+    se = ez.sum(dim=1, keepdim=True)
+    onehot = torch.zeros_like(ez).scatter_(1, labels.view(-1, 1), 1.0)
+    loss = -((z - se.log()) * onehot).sum() / B
+    correct = (logits.argmax(dim=1) == labels).double().sum()
+    d = (ez / se - onehot) / B
+    db2 = d.sum(dim=0)
+    dl = d.to(a1.dtype).double()
+    dw2 = af.t() @ dl
+    g = (dl @ wf.t()) * (a1 > 0) / p_keep
+    db1 = g.sum(dim=0)
+    return loss, correct, g.to(a1.dtype), dw2, db1, db2
+
+
 # ---------------------------------------------------------------------------
 # Fused SGD apply (+ drop-connect): distributed_train.py:176,414-416
 # ---------------------------------------------------------------------------

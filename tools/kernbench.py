@@ -91,6 +91,7 @@ def bench_batch(ext, B):
         ("fc2 dW", lambda: ext.linear_dw_into(a1, dyeff2, dw2f)),
         ("fc2 dX", lambda: ext.linear_dx(dyeff2, f2)),
         ("fc2 dX+mask+db fused", lambda: ext.linear_dx_mask(dl, f2, a1, db1f, 0.5)),
+        ("fc2 head: fwd + softmax-CE + dW + dX+mask+db, one launch (DMNIST_FC2_FUSED=0: the four above)", lambda: ext.fc2_head(a1, f2, f2T, fb2, labels, dw2f, db2f, db1f, 0.5, 1.0 / B)),
         ("mask+db (fc1)", lambda: ext.mask_db(dx2, a1, True, 0.5, db1f)),
         ("fc1 dW (A_T split-K)", lambda: ext.linear_dw_into(h2, dyeff1, dw1f)),
         ("fc1 dX", lambda: ext.linear_dx(dyeff1, f1)),
