@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cmath>
 #include <map>
 #include <tuple>
 
@@ -1126,11 +1127,23 @@ static float* momentum_ptr(const c10::optional<torch::Tensor>& momentum) {
   return momentum->data_ptr<float>();
 }
 
+// optional clip coefficient of the SGD pass (grad_norm's stats[1:2], read on
+// the device): nullptr = the pass without clipping
+static const float* clip_coef_ptr(const c10::optional<torch::Tensor>& coef,
+                                  const torch::Tensor& master) {
+  if (!coef.has_value() || !coef->defined()) return nullptr;
+  CHECK_CUDA((*coef)); CHECK_F32((*coef));
+  TORCH_CHECK(coef->numel() == 1 && coef->get_device() == master.get_device(),
+              "sgd_step: clip_coef is one fp32 value on master's device");
+  return coef->data_ptr<float>();
+}
+
 void sgd_step(torch::Tensor master, torch::Tensor grad, torch::Tensor shadow,
               bool has_shadow, double lr, double scale, double dc_keep,
               int64_t seed, int64_t offset,
               c10::optional<torch::Tensor> momentum, double mu,
-              c10::optional<torch::Tensor> ema, double ema_decay) {
+              c10::optional<torch::Tensor> ema, double ema_decay,
+              c10::optional<torch::Tensor> clip_coef) {
   CHECK_CUDA(master); CHECK_F32(master); CHECK_CONTIG(master);
   CHECK_F32(grad); CHECK_CONTIG(grad);
   float* mom = momentum_ptr(momentum);
@@ -1140,7 +1153,7 @@ void sgd_step(torch::Tensor master, torch::Tensor grad, torch::Tensor shadow,
                   has_shadow ? 1 : 0, master.numel(),
                   (float)(lr * scale), (float)dc_keep, (uint64_t)seed,
                   (uint64_t)offset, mom, (float)mu, emap, (float)ema_decay,
-                  cur_stream());
+                  clip_coef_ptr(clip_coef, master), cur_stream());
 }
 
 void sgd_step_dev(torch::Tensor master, torch::Tensor grad,
@@ -1149,7 +1162,7 @@ void sgd_step_dev(torch::Tensor master, torch::Tensor grad,
                   torch::Tensor offset_dev,
                   c10::optional<torch::Tensor> momentum, double mu,
                   bool zero_grad, c10::optional<torch::Tensor> ema,
-                  double ema_decay) {
+                  double ema_decay, c10::optional<torch::Tensor> clip_coef) {
   CHECK_CUDA(master); CHECK_F32(master); CHECK_CONTIG(master);
   CHECK_F32(grad); CHECK_CONTIG(grad);
   CHECK_F32(lr_scale_dev);
@@ -1161,7 +1174,60 @@ void sgd_step_dev(torch::Tensor master, torch::Tensor grad,
                       (uint64_t)seed, offset_dev.data_ptr<long>(),
                       mom, (float)mu, zero_grad ? 1 : 0,
                       ema_ptr(ema, master, ema_decay), (float)ema_decay,
-                      cur_stream());
+                      clip_coef_ptr(clip_coef, master), cur_stream());
+}
+
+// Per-tensor and global gradient norms + the clip coefficient of the flat
+// fp32 bucket, on the device (grad_norm.hip).  offsets/numels: the tensors of
+// FlatParams; they must tile [0, grad.numel()) in order.
+void grad_norm(torch::Tensor grad, std::vector<int64_t> offsets,
+               std::vector<int64_t> numels, double grad_scale, double clip,
+               torch::Tensor stats, torch::Tensor clipped_steps) {
+  CHECK_CUDA(grad); CHECK_F32(grad); CHECK_CONTIG(grad);
+  CHECK_CUDA(stats); CHECK_F32(stats); CHECK_CONTIG(stats);
+  CHECK_CUDA(clipped_steps); CHECK_CONTIG(clipped_steps);
+  TORCH_CHECK(clipped_steps.scalar_type() == at::kLong &&
+              clipped_steps.numel() == 1,
+              "grad_norm: clipped_steps is one int64");
+  const int64_t n = grad.numel();
+  const size_t ns = offsets.size();
+  TORCH_CHECK(n >= 1, "grad_norm: empty gradient");
+  TORCH_CHECK(ns >= 1 && ns <= GRAD_NORM_MAX_SEGS && numels.size() == ns,
+              "grad_norm: 1 to ", GRAD_NORM_MAX_SEGS,
+              " segments, one length per offset");
+  TORCH_CHECK(stats.numel() == (int64_t)(2 + ns),
+              "grad_norm: stats holds 2 + segments values");
+  TORCH_CHECK(stats.get_device() == grad.get_device() &&
+              clipped_steps.get_device() == grad.get_device(),
+              "grad_norm: stats and clipped_steps live on grad's device");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(grad.data_ptr()) % 16 == 0,
+              "grad_norm: grad must be 16-byte aligned");
+  TORCH_CHECK(clip > 0.0, "grad_norm: clip must be > 0 (inf = never clip)");
+  TORCH_CHECK(grad_scale > 0.0 && std::isfinite(grad_scale),
+              "grad_norm: grad_scale must be finite and > 0");
+  GradNormSegs segs{};
+  int64_t at = 0;
+  for (size_t i = 0; i < ns; ++i) {
+    TORCH_CHECK(offsets[i] == at && numels[i] >= 0,
+                "grad_norm: the segments must tile [0, n) in order");
+    segs.off[i] = offsets[i];
+    segs.len[i] = numels[i];
+    at += numels[i];
+  }
+  TORCH_CHECK(at == n, "grad_norm: the segments must tile [0, n) in order");
+  segs.n = (int)ns;
+  auto s = cur_stream();
+  static auto* ws = new WorkspaceSlots(64);
+  float* part = device_workspace(
+      *ws, grad, GRAD_NORM_MAX_SEGS * GRAD_NORM_MAX_BLOCKS + 1, at::kFloat, s,
+      "grad_norm",
+      "grad_norm: first call on a device allocates its workspace and must "
+      "run outside graph capture").data_ptr<float>();
+  unsigned* ticket = reinterpret_cast<unsigned*>(
+      part + GRAD_NORM_MAX_SEGS * GRAD_NORM_MAX_BLOCKS);
+  launch_grad_norm(grad.data_ptr<float>(), n, segs, (float)grad_scale,
+                   (float)clip, stats.data_ptr<float>(),
+                   clipped_steps.data_ptr<long>(), part, ticket, s);
 }
 
 void ema_publish(torch::Tensor ema, torch::Tensor shadow,
@@ -1524,7 +1590,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("has_shadow"), py::arg("lr"), py::arg("scale"),
         py::arg("dc_keep"), py::arg("seed"), py::arg("offset"),
         py::arg("momentum") = c10::nullopt, py::arg("mu") = 0.0,
-        py::arg("ema") = c10::nullopt, py::arg("ema_decay") = 0.0);
+        py::arg("ema") = c10::nullopt, py::arg("ema_decay") = 0.0,
+        py::arg("clip_coef") = c10::nullopt);
+  m.def("grad_norm", &grad_norm,
+        "stats[0] = grad_scale * |grad|, stats[1] = min(1, clip / (stats[0] "
+        "+ 1e-6)), stats[2 + s] = grad_scale * |segment s|; clipped_steps "
+        "+= 1 when stats[1] < 1; one launch, no float atomics",
+        py::arg("grad"), py::arg("offsets"), py::arg("numels"),
+        py::arg("grad_scale"), py::arg("clip"), py::arg("stats"),
+        py::arg("clipped_steps"));
+  m.def("grad_norm_plan", [](int64_t n) {
+          TORCH_CHECK(n >= 1, "grad_norm_plan: n must be >= 1");
+          int blocks, chain;
+          grad_norm_plan((long)n, &blocks, &chain);
+          return std::make_tuple(blocks, chain);
+        }, "(blocks, chain) of grad_norm on n elements: the grid, and the "
+        "longest run of fp32 additions any element passes through");
   m.def("ema_publish", &ema_publish,
         "flat fp32 parameters -> flat bf16 shadow + transposed bf16 copies "
         "of the [rows][cols] slices at `offsets`, one launch",
@@ -1538,7 +1619,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("seed"), py::arg("offset_dev"),
         py::arg("momentum") = c10::nullopt, py::arg("mu") = 0.0,
         py::arg("zero_grad") = false,
-        py::arg("ema") = c10::nullopt, py::arg("ema_decay") = 0.0);
+        py::arg("ema") = c10::nullopt, py::arg("ema_decay") = 0.0,
+        py::arg("clip_coef") = c10::nullopt);
   m.def("step_advance", &step_advance,
         "device-side staircase LR + step increment (inside the graph)");
   m.def("grad_mask", &grad_mask,

@@ -26,7 +26,7 @@ def main():
     srcs = [os.path.join(ROOT, f) for f in
             ("gemm_tile.hip", "conv_slab.hip", "dw_tr.hip", "ops_misc.hip", "conv1_mfma.hip",
              "data_gather.hip", "conv2_dw_slab.hip", "eval_ops.hip",
-             "det_reduce.hip", "fc2_head.hip",
+             "det_reduce.hip", "fc2_head.hip", "grad_norm.hip",
              "bindings.cpp")]
     out = os.path.join(ROOT, "_dmnist_hip.so")
 

@@ -106,14 +106,45 @@ void launch_fc2_head(int R, const unsigned short* a1,
 void launch_sgd_step(float* master, float* grad, unsigned short* shadow,
                      int has_shadow, long n, float lr_scale, float dc_keep,
                      uint64_t seed, uint64_t offset, float* momentum, float mu,
-                     float* ema, float ema_decay, hipStream_t);
+                     float* ema, float ema_decay, const float* clip_coef_dev,
+                     hipStream_t);
 // graph-capturable variants: lr_scale / RNG offset read from device memory
 void launch_sgd_step_dev(float* master, float* grad,
                          unsigned short* shadow, int has_shadow, long n,
                          const float* lr_scale_dev, float dc_keep,
                          uint64_t seed, const long* offset_dev,
                          float* momentum, float mu, int zero_grad,
-                         float* ema, float ema_decay, hipStream_t);
+                         float* ema, float ema_decay,
+                         const float* clip_coef_dev, hipStream_t);
+// clip_coef_dev != nullptr (both launchers): the gradient is multiplied by
+// *clip_coef_dev (launch_grad_norm's stats[1]) before the drop-connect mask
+// and the momentum filter, v = mu*v + coef*g (two more instantiations;
+// nullptr launches the unchanged sgd_step_kernel / sgd_step_kernel_ema).
+// grad_norm.hip — per-tensor and global norms of the flat fp32 gradient and
+// the clip_grad_norm_ coefficient, one launch, no float atomics.  segs: up to
+// GRAD_NORM_MAX_SEGS (element offset, length) pairs that tile [0, n) in
+// order; grad 16 B aligned.  STORED (no pre-zeroing): stats[0] = grad_scale *
+// sqrt(sum g^2), stats[1] = fminf(1, clip / (stats[0] + 1e-6f)) (clip = +inf
+// gives exactly 1), stats[2 + s] = grad_scale * sqrt(sum of g^2 over segment
+// s); *clipped_steps += 1 when stats[1] < 1.  part/ticket: a persistent
+// workspace of GRAD_NORM_MAX_SEGS * GRAD_NORM_MAX_BLOCKS floats + one
+// zero-initialised, self-resetting counter (launches on one device must not
+// overlap).  The result is a pure function of (grad, n, segs, geometry).
+#define GRAD_NORM_MAX_SEGS 16
+#define GRAD_NORM_MAX_BLOCKS 1024
+#define GRAD_NORM_CHUNK 4096  // elements per block up to MAX_BLOCKS chunks
+struct GradNormSegs {
+  long off[GRAD_NORM_MAX_SEGS];
+  long len[GRAD_NORM_MAX_SEGS];
+  int n;
+};
+// grid of the launch and the longest run of fp32 additions any element
+// passes through (the error bound of the norms is chain + 4 roundings)
+void grad_norm_plan(long n, int* blocks, int* chain);
+void launch_grad_norm(const float* grad, long n, GradNormSegs segs,
+                      float grad_scale, float clip, float* stats,
+                      long* clipped_steps, float* part, unsigned* ticket,
+                      hipStream_t);
 // ema != nullptr (both launchers): the same pass also moves the fp32 moving
 // average towards the new master, e -= (1 - d_k)*(e - w) with
 // d_k = min(ema_decay, (1 + k)/(10 + k)), k = offset + 1 (a second

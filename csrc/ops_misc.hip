@@ -308,13 +308,18 @@ void softmax_xent_t_kernel(const ushort_t* logits, const long* labels,
 // (1 + k)/(10 + k)) — one more fp32 read-modify-write stream in the same
 // pass, fed from the master already in registers.  EMA = false compiles to
 // exactly the pass without it.
-template <bool EMA>
+// CLIP (compile-time variant, --clip_grad_norm): the gradient is multiplied
+// by `coef` (grad_norm_kernel's clip coefficient, read once per thread by the
+// caller) first: before the drop-connect mask and before momentum,
+// v = mu*v + coef*g.  CLIP = false compiles to exactly the pass without it.
+template <bool EMA, bool CLIP = false>
 __device__ __forceinline__
 void sgd_step_body(float* master, float* grad, ushort_t* shadow,
                    int has_shadow, long n, float lr_scale, float dc_keep,
                    uint64_t seed, uint64_t offset,
                    float* momentum, float mu, int zero_grad,
-                   float* ema, float ema_decay, long i, long stride) {
+                   float* ema, float ema_decay, long i, long stride,
+                   float coef = 1.f) {
   // lr_scale / offset: already resolved from their device copies;
   // i / stride: the caller's grid-stride start and step, in float4 groups
   // (blockDim read in here costs a run-time workgroup-size lookup that the
@@ -334,6 +339,7 @@ void sgd_step_body(float* master, float* grad, ushort_t* shadow,
     if (base + 3 < n) {
       float4 g = *reinterpret_cast<const float4*>(grad + base);
       float4 m = *reinterpret_cast<const float4*>(master + base);
+      if (CLIP) { g.x *= coef; g.y *= coef; g.z *= coef; g.w *= coef; }
       if (dc_keep > 0.f) {
         Philox4 ph = philox4x32(seed, offset, (uint64_t)i);
         const float s = 1.0f / 4294967296.0f;
@@ -370,6 +376,7 @@ void sgd_step_body(float* master, float* grad, ushort_t* shadow,
       float u[4] = {ph.x * s, ph.y * s, ph.z * s, ph.w * s};
       for (long j = base; j < n; ++j) {
         float g = grad[j];
+        if (CLIP) g *= coef;
         if (dc_keep > 0.f) g *= (u[j - base] < dc_keep) ? 1.f : 0.f;
         if (momentum) {
           float v = mu * momentum[j] + g;
@@ -416,6 +423,39 @@ void sgd_step_kernel_ema(float* master, float* grad, ushort_t* shadow,
                       seed, offset, momentum, mu, zero_grad, ema, ema_decay,
                       (long)(blockIdx.x) * blockDim.x + threadIdx.x,
                       (long)gridDim.x * blockDim.x);
+}
+
+extern "C" __global__ __launch_bounds__(256)
+void sgd_step_kernel_clip(float* master, float* grad, ushort_t* shadow,
+                          int has_shadow, long n, float lr_scale, float dc_keep,
+                          uint64_t seed, uint64_t offset,
+                          const float* lr_scale_dev, const long* offset_dev,
+                          float* momentum, float mu, int zero_grad,
+                          const float* clip_coef_dev) {
+  if (lr_scale_dev) lr_scale = *lr_scale_dev;
+  if (offset_dev) offset = (uint64_t)*offset_dev;
+  sgd_step_body<false, true>(master, grad, shadow, has_shadow, n, lr_scale,
+                             dc_keep, seed, offset, momentum, mu, zero_grad,
+                             nullptr, 0.f,
+                             (long)(blockIdx.x) * blockDim.x + threadIdx.x,
+                             (long)gridDim.x * blockDim.x, *clip_coef_dev);
+}
+
+extern "C" __global__ __launch_bounds__(256)
+void sgd_step_kernel_clip_ema(float* master, float* grad, ushort_t* shadow,
+                              int has_shadow, long n, float lr_scale,
+                              float dc_keep, uint64_t seed, uint64_t offset,
+                              const float* lr_scale_dev,
+                              const long* offset_dev, float* momentum,
+                              float mu, int zero_grad, float* ema,
+                              float ema_decay, const float* clip_coef_dev) {
+  if (lr_scale_dev) lr_scale = *lr_scale_dev;
+  if (offset_dev) offset = (uint64_t)*offset_dev;
+  sgd_step_body<true, true>(master, grad, shadow, has_shadow, n, lr_scale,
+                            dc_keep, seed, offset, momentum, mu, zero_grad,
+                            ema, ema_decay,
+                            (long)(blockIdx.x) * blockDim.x + threadIdx.x,
+                            (long)gridDim.x * blockDim.x, *clip_coef_dev);
 }
 
 // step/LR advance: device-side staircase LR so a captured graph needs no
@@ -564,23 +604,48 @@ void launch_softmax_xent(const unsigned short* logits, const long* labels,
                        ticket);
 }
 
-void launch_sgd_step(float* master, float* grad, unsigned short* shadow,
-                     int has_shadow, long n, float lr_scale, float dc_keep,
-                     uint64_t seed, uint64_t offset, float* momentum, float mu,
-                     float* ema, float ema_decay, hipStream_t s) {
+// the one launch of the SGD pass: clip_coef_dev picks the clipped
+// instantiations, nullptr the kernels (and argument lists) without it
+static void sgd_step_launch(float* master, float* grad, unsigned short* shadow,
+                            int has_shadow, long n, float lr_scale,
+                            float dc_keep, uint64_t seed, uint64_t offset,
+                            const float* lr_scale_dev, const long* offset_dev,
+                            float* momentum, float mu, int zero_grad,
+                            float* ema, float ema_decay,
+                            const float* clip_coef_dev, hipStream_t s) {
   long groups = (n + 3) / 4;
   int blocks = (int)min((long)2048, (groups + 255) / 256);
   if (blocks < 1) blocks = 1;
-  if (ema)
+  if (clip_coef_dev && ema)
+    hipLaunchKernelGGL(sgd_step_kernel_clip_ema, dim3(blocks), dim3(256), 0, s,
+                       master, grad, shadow, has_shadow, n, lr_scale, dc_keep,
+                       seed, offset, lr_scale_dev, offset_dev, momentum, mu,
+                       zero_grad, ema, ema_decay, clip_coef_dev);
+  else if (clip_coef_dev)
+    hipLaunchKernelGGL(sgd_step_kernel_clip, dim3(blocks), dim3(256), 0, s,
+                       master, grad, shadow, has_shadow, n, lr_scale, dc_keep,
+                       seed, offset, lr_scale_dev, offset_dev, momentum, mu,
+                       zero_grad, clip_coef_dev);
+  else if (ema)
     hipLaunchKernelGGL(sgd_step_kernel_ema, dim3(blocks), dim3(256), 0, s,
                        master, grad, shadow, has_shadow, n, lr_scale, dc_keep,
-                       seed, offset, (const float*)nullptr,
-                       (const long*)nullptr, momentum, mu, 0, ema, ema_decay);
+                       seed, offset, lr_scale_dev, offset_dev, momentum, mu,
+                       zero_grad, ema, ema_decay);
   else
     hipLaunchKernelGGL(sgd_step_kernel, dim3(blocks), dim3(256), 0, s, master,
                        grad, shadow, has_shadow, n, lr_scale, dc_keep, seed,
-                       offset, (const float*)nullptr, (const long*)nullptr,
-                       momentum, mu, 0);
+                       offset, lr_scale_dev, offset_dev, momentum, mu,
+                       zero_grad);
+}
+
+void launch_sgd_step(float* master, float* grad, unsigned short* shadow,
+                     int has_shadow, long n, float lr_scale, float dc_keep,
+                     uint64_t seed, uint64_t offset, float* momentum, float mu,
+                     float* ema, float ema_decay, const float* clip_coef_dev,
+                     hipStream_t s) {
+  sgd_step_launch(master, grad, shadow, has_shadow, n, lr_scale, dc_keep, seed,
+                  offset, nullptr, nullptr, momentum, mu, 0, ema, ema_decay,
+                  clip_coef_dev, s);
 }
 
 void launch_sgd_step_dev(float* master, float* grad,
@@ -588,19 +653,11 @@ void launch_sgd_step_dev(float* master, float* grad,
                          const float* lr_scale_dev, float dc_keep,
                          uint64_t seed, const long* offset_dev,
                          float* momentum, float mu, int zero_grad,
-                         float* ema, float ema_decay, hipStream_t s) {
-  long groups = (n + 3) / 4;
-  int blocks = (int)min((long)2048, (groups + 255) / 256);
-  if (blocks < 1) blocks = 1;
-  if (ema)
-    hipLaunchKernelGGL(sgd_step_kernel_ema, dim3(blocks), dim3(256), 0, s,
-                       master, grad, shadow, has_shadow, n, 0.f, dc_keep, seed,
-                       0, lr_scale_dev, offset_dev, momentum, mu, zero_grad,
-                       ema, ema_decay);
-  else
-    hipLaunchKernelGGL(sgd_step_kernel, dim3(blocks), dim3(256), 0, s, master,
-                       grad, shadow, has_shadow, n, 0.f, dc_keep, seed, 0,
-                       lr_scale_dev, offset_dev, momentum, mu, zero_grad);
+                         float* ema, float ema_decay,
+                         const float* clip_coef_dev, hipStream_t s) {
+  sgd_step_launch(master, grad, shadow, has_shadow, n, 0.f, dc_keep, seed, 0,
+                  lr_scale_dev, offset_dev, momentum, mu, zero_grad, ema,
+                  ema_decay, clip_coef_dev, s);
 }
 
 // ---------------------------------------------------------------------------

@@ -97,6 +97,11 @@ class GraphedStep:
                 if getattr(t, "flat_momentum", None) is not None else None)
         ema0 = (t.flat_ema.clone()
                 if getattr(t, "flat_ema", None) is not None else None)
+        # --clip_grad_norm: the warmup's gradients are clipped and counted too
+        self._clip_stats = getattr(t, "clip_stats", None)
+        clip0 = None
+        if self._clip_stats is not None:
+            clip0 = (self._clip_stats.clone(), t.clipped_steps.clone())
         t.model.set_step_dev(self.step_dev)
 
         if self.split and self._fused is not None:
@@ -219,6 +224,9 @@ class GraphedStep:
                     t.flat_momentum.copy_(mom0)
                 if ema0 is not None:
                     t.flat_ema.copy_(ema0)
+                if clip0 is not None:
+                    self._clip_stats.copy_(clip0[0])
+                    t.clipped_steps.copy_(clip0[1])
                 t.fp.sync_shadow()
                 t.model.set_step(t.step)
             except Exception:
@@ -234,6 +242,9 @@ class GraphedStep:
             t.flat_momentum.copy_(mom0)
         if ema0 is not None:
             t.flat_ema.copy_(ema0)
+        if clip0 is not None:
+            self._clip_stats.copy_(clip0[0])
+            t.clipped_steps.copy_(clip0[1])
         t.fp.sync_shadow()
         self._prime(t.step)
         torch.cuda.synchronize()
@@ -282,6 +293,16 @@ class GraphedStep:
         this is capturable AND replay-equivalent when run eagerly)."""
         t = self.t
         fp = t.fp
+        clip_coef = None
+        if self._clip_stats is not None:
+            # norms + clip coefficient of the aggregated bucket, on the
+            # device; every argument is device-resident or a capture
+            # constant.  Its first call (warmup) runs outside capture and
+            # allocates the kernel's workspace.
+            self._ext.grad_norm(fp.flat_grad, fp.offsets, fp.numels,
+                                self.inv_contrib, t.clip, self._clip_stats,
+                                t.clipped_steps)
+            clip_coef = self._clip_stats[1:2]
         # zero_grad=True: the bucket is cleared in the same pass that
         # consumes it — no per-step fill kernel in the replayed graph
         self._ext.sgd_step_dev(fp.flat_master, fp.flat_grad,
@@ -293,7 +314,8 @@ class GraphedStep:
                                momentum=t.flat_momentum,
                                mu=t.flags.momentum, zero_grad=True,
                                ema=getattr(t, "flat_ema", None),
-                               ema_decay=getattr(t, "ema_decay", 0.0))
+                               ema_decay=getattr(t, "ema_decay", 0.0),
+                               clip_coef=clip_coef)
         if fp._t_pairs:
             # transposes + step/LR advance in ONE dispatch
             self._ext.transpose_bf16_batch_adv(

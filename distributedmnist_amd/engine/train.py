@@ -212,6 +212,28 @@ class Trainer:
                                      compute_dtype=self.compute_dtype)
             self.flat_ema = self.ema_fp.flat_master
             self.flat_ema.copy_(self.fp.flat_master)
+        # --clip_grad_norm C > 0: global-norm clipping of the aggregated
+        # gradient (torch.nn.utils.clip_grad_norm_ semantics).  grad_norm
+        # reduces the bucket to clip_stats on the device (global norm, clip
+        # coefficient, one norm per tensor) and the SGD pass reads the
+        # coefficient there.  The norm is taken AFTER aggregation: every rank
+        # holds the same bucket and computes the same coefficient, so there is
+        # no collective; pre-aggregation drop-connect masks are already in the
+        # bucket, the post-aggregation mask comes after the clip.  inf never
+        # clips (norm telemetry only).  Nothing of this is checkpointed.
+        self.clip = float(getattr(flags, "clip_grad_norm", 0.0) or 0.0)
+        if not self.clip >= 0.0:
+            raise ValueError("--clip_grad_norm must be 0 (off) or > 0, "
+                             f"got {self.clip}")
+        self.clip_stats = self.clipped_steps = None
+        self.clip_updates = 0  # updates applied: what clipped_steps is out of
+        if self.clip > 0:
+            self.clip_stats = torch.zeros(2 + len(self.fp.names),
+                                          dtype=torch.float32,
+                                          device=self.device)
+            self.clip_stats[1] = 1.0
+            self.clipped_steps = torch.zeros(1, dtype=torch.int64,
+                                             device=self.device)
 
     # ------------------------------------------------------------------
     def to_device(self, images, labels):
@@ -344,8 +366,10 @@ class Trainer:
             self._cdf_steps.append(step)
             if len(self._cdf_steps) >= self.engine.cdf_log_every:
                 self._flush_cdf()
+            self.clip_updates += 1
             return True, loss, acc, 0.0
         loss, acc = replay()
+        self.clip_updates += 1
         return True, loss, acc, 0.0
 
     # -- batched CDF timing for the graph path -------------------------
@@ -447,6 +471,14 @@ class Trainer:
             lr_step = self.step
         lr = lr_at(lr_step, flags, self._num_examples,
                    max(1, self.engine.K))
+        clip_coef = None
+        if self.clip_stats is not None:
+            Fx.grad_norm(grad, self.fp.offsets, self.fp.numels,
+                         1.0 / max(1, contributors), self.clip,
+                         stats=self.clip_stats,
+                         clipped_steps=self.clipped_steps)
+            clip_coef = self.clip_stats[1:2]
+        self.clip_updates += 1
         Fx.sgd_step(self.fp.flat_master, grad, lr,
                     grad_scale=1.0 / max(1, contributors),
                     drop_connect_keep=(flags.drop_connect_probability
@@ -455,9 +487,24 @@ class Trainer:
                     seed=flags.seed, offset=lr_step,
                     shadow=self.fp.flat_shadow,
                     momentum=self.flat_momentum, mu=flags.momentum,
-                    ema=self.flat_ema, ema_decay=self.ema_decay)
+                    ema=self.flat_ema, ema_decay=self.ema_decay,
+                    clip_coef=clip_coef)
         self.fp.refresh_transposes()
         self.num_contributors = contributors
+
+    def grad_norms(self):
+        """Norms of the most recent aggregated (averaged) gradient under
+        --clip_grad_norm: {tensor name: L2 norm} plus "global" (the norm the
+        clip compares with its threshold) and "clip_coef" (the factor that
+        gradient was scaled by).  Reads the device: for tools and tests, not
+        for the step loop."""
+        if self.clip_stats is None:
+            raise RuntimeError("grad_norms() needs --clip_grad_norm > 0 "
+                               "(inf = norms only, never clips)")
+        s = self.clip_stats.detach().cpu().tolist()
+        out = {name: s[2 + i] for i, name in enumerate(self.fp.names)}
+        out["global"], out["clip_coef"] = s[0], s[1]
+        return out
 
     # -- in-training evaluation (--eval_every_steps) ----------------------
     def attach_eval_dataset(self, ds):
@@ -596,6 +643,13 @@ class Trainer:
                 writer.add_scalar("Train Loss", loss_v, self.step)
                 writer.add_scalar("Train Accuracy", acc_v, self.step)
                 writer.add_scalar("Examples/sec", examples_per_sec, self.step)
+                if self.clip_stats is not None:
+                    # read only here, where a summary is written
+                    norms = self.grad_norms()
+                    writer.add_scalar("Gradient Norm", norms["global"],
+                                      self.step)
+                    writer.add_scalar("Clip Coefficient", norms["clip_coef"],
+                                      self.step)
                 next_summary_time += flags.save_summaries_secs
             sv.maybe_save(self.step, self.checkpoint_payload)
         if self.mode == "interval":
@@ -610,6 +664,10 @@ class Trainer:
             writer.close()
         if self.is_chief:
             log.info("Elapsed Time: %f", time.time() - begin_time)
+            if self.clipped_steps is not None:
+                log.info("Gradient clipping (--clip_grad_norm %g): %d of %d "
+                         "updates clipped", self.clip,
+                         int(self.clipped_steps.item()), self.clip_updates)
             sv.save(self.step, self.checkpoint_payload())
         if self.world > 1 and dist.is_initialized():
             dist.barrier()

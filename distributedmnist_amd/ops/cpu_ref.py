@@ -192,8 +192,12 @@ def sgd_step(master, grad, lr: float, grad_scale: float = 1.0,
              drop_connect_keep: float | None = None,
              gen: torch.Generator | None = None, shadow=None,
              momentum=None, mu: float = 0.0, ema=None,
-             ema_decay: float = 0.0, offset: int = 0):
+             ema_decay: float = 0.0, offset: int = 0, clip_coef=None):
     """In-place w -= lr * grad_scale * (g or momentum-filtered g).
+
+    clip_coef: optional one-element fp32 tensor (grad_norm()'s stats[1:2]);
+    the gradient is multiplied by it first, before the drop-connect mask and
+    before momentum: v = mu*v + coef*g.
 
     drop_connect_keep: if set, per-element Bernoulli(keep) mask on the grad
     (reference drop_connect: grad * mask, NO rescale —
@@ -208,6 +212,8 @@ def sgd_step(master, grad, lr: float, grad_scale: float = 1.0,
     (1 + k)/(10 + k)), everything in fp32.
     """
     g = grad.float() * grad_scale
+    if clip_coef is not None:
+        g = g * clip_coef.float().reshape(())
     if drop_connect_keep is not None:
         mask = (torch.rand(g.shape, device=g.device, dtype=torch.float32,
                            generator=gen) < drop_connect_keep).float()
@@ -221,6 +227,54 @@ def sgd_step(master, grad, lr: float, grad_scale: float = 1.0,
     if shadow is not None:
         shadow.copy_(master.to(shadow.dtype))
     return master
+
+
+def grad_norm(flat, offsets, numels, grad_scale: float, clip: float):
+    """Per-tensor and global L2 norms of a flat fp32 gradient and the
+    torch.nn.utils.clip_grad_norm_ coefficient -> fp32 `stats` [2 + segments]
+    on flat's device, the layout of csrc/grad_norm.hip:
+
+      stats[0]     = grad_scale * sqrt(sum of g^2)       (the global norm)
+      stats[1]     = min(1, clip / (stats[0] + 1e-6))    (fp32 arithmetic)
+      stats[2 + s] = grad_scale * sqrt(sum of g^2 over segment s)
+
+    The sums of squares are taken per segment in float64 from the fp32
+    values, the total is their float64 sum, the norms are rounded to fp32.
+    `flat` is the SUM over contributors, grad_scale = 1 / contributors, so the
+    norms are those of the averaged gradient.  The segments (offsets, numels)
+    must tile [0, flat.numel()) in order; clip > 0, inf = never clip (the
+    coefficient is then exactly 1)."""
+    import numpy as np
+    n = flat.numel()
+    if flat.dtype != torch.float32 or flat.dim() != 1:
+        raise ValueError("grad_norm: flat must be a 1-D fp32 tensor")
+    if not (len(offsets) == len(numels) and len(offsets) >= 1):
+        raise ValueError("grad_norm: one length per offset, at least one")
+    at = 0
+    for o, m in zip(offsets, numels):
+        if o != at or m < 0:
+            raise ValueError("grad_norm: the segments must tile [0, n) in "
+                             "order")
+        at += m
+    if at != n:
+        raise ValueError("grad_norm: the segments must tile [0, n) in order")
+    if not clip > 0.0:  # also refuses nan
+        raise ValueError(f"grad_norm: clip must be > 0, got {clip}")
+    g = flat.detach().double()
+    sq = [float((g[o:o + m] * g[o:o + m]).sum())
+          for o, m in zip(offsets, numels)]
+    total = 0.0
+    for v in sq:
+        total += v
+    f32 = np.float32
+    with np.errstate(over="ignore", invalid="ignore"):
+        norm = f32(float(grad_scale) * np.sqrt(total))
+        coef = np.minimum(f32(1), f32(clip) / (norm + f32(1e-6)))
+        if np.isnan(coef):
+            coef = f32(1)  # fminf(1, nan)
+    out = [norm, coef] + [f32(float(grad_scale) * np.sqrt(v)) for v in sq]
+    return torch.tensor([float(v) for v in out], dtype=torch.float32,
+                        device=flat.device)
 
 
 def ema_weight(ema_decay: float, offset: int) -> float:

@@ -272,12 +272,45 @@ def softmax_eval(logits: torch.Tensor, labels: torch.Tensor,
                              cursor_dev=cursor_dev)
 
 
+def grad_norm(flat: torch.Tensor, offsets, numels, grad_scale: float,
+              clip: float, stats=None, clipped_steps=None):
+    """Per-tensor and global L2 norms of the flat fp32 gradient `flat` (the
+    SUM over contributors, grad_scale = 1 / contributors) and the
+    clip_grad_norm_ coefficient -> `stats` (fp32 [2 + segments]: norm,
+    min(1, clip / (norm + 1e-6)), then one norm per (offset, numel) segment;
+    ops/cpu_ref.py::grad_norm).  `stats` is written in place when given;
+    `clipped_steps` (int64 [1], optional) counts the calls whose coefficient
+    is below 1.  On the GPU one grad_norm_kernel launch: device-resident,
+    hipGraph-capturable (after a first call outside capture), no float
+    atomics, so equal inputs give equal bits."""
+    offsets, numels = [int(o) for o in offsets], [int(m) for m in numels]
+    if stats is None:
+        stats = torch.empty(2 + len(offsets), dtype=torch.float32,
+                            device=flat.device)
+    if flat.is_cuda:
+        if clipped_steps is None:
+            clipped_steps = torch.zeros(1, dtype=torch.int64,
+                                        device=flat.device)
+        _C.ext().grad_norm(flat, offsets, numels, float(grad_scale),
+                           float(clip), stats, clipped_steps)
+    else:
+        stats.copy_(cpu_ref.grad_norm(flat, offsets, numels, grad_scale,
+                                      clip))
+        if clipped_steps is not None and float(stats[1]) < 1.0:
+            clipped_steps += 1
+    return stats
+
+
 def sgd_step(master: torch.Tensor, grad: torch.Tensor, lr: float,
              grad_scale: float = 1.0, drop_connect_keep=None,
              seed: int = 0, offset: int = 0, shadow=None,
              momentum=None, mu: float = 0.0, ema=None,
-             ema_decay: float = 0.0):
+             ema_decay: float = 0.0, clip_coef=None):
     """Fused flat SGD apply: master -= lr*scale*(grad [* bernoulli(keep)]).
+
+    `clip_coef` (optional one-element fp32 tensor on master's device,
+    grad_norm()'s stats[1:2]) multiplies the gradient first, before the
+    drop-connect mask and before momentum; it is read on the device.
 
     Optionally refreshes the bf16 `shadow` copy (one kernel on GPU).
     Reference semantics: GradientDescentOptimizer + drop_connect mask with NO
@@ -295,7 +328,7 @@ def sgd_step(master: torch.Tensor, grad: torch.Tensor, lr: float,
                           -1.0 if drop_connect_keep is None else float(drop_connect_keep),
                           int(seed), int(offset),
                           momentum=momentum, mu=float(mu), ema=ema,
-                          ema_decay=float(ema_decay))
+                          ema_decay=float(ema_decay), clip_coef=clip_coef)
     else:
         gen = None
         if drop_connect_keep is not None:
@@ -304,4 +337,5 @@ def sgd_step(master: torch.Tensor, grad: torch.Tensor, lr: float,
         cpu_ref.sgd_step(master, grad, lr, grad_scale,
                          drop_connect_keep, gen, shadow,
                          momentum=momentum, mu=mu, ema=ema,
-                         ema_decay=ema_decay, offset=offset)
+                         ema_decay=ema_decay, offset=offset,
+                         clip_coef=clip_coef)

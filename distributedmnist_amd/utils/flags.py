@@ -26,6 +26,18 @@ def _decay(text: str) -> float:
     return v
 
 
+def _clip(text: str) -> float:
+    """--clip_grad_norm: 0 (off) or a threshold > 0, inf included."""
+    try:
+        v = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a number: {text!r}")
+    if not v >= 0.0:  # also refuses nan
+        raise argparse.ArgumentTypeError(
+            f"must be 0 (off) or > 0 (inf = never clip), got {text}")
+    return v
+
+
 def build_train_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="MI355X-native distributed MNIST training")
     # --- reference-compatible flags (distributed_train.py:36-99) ---
@@ -134,6 +146,14 @@ def build_train_parser() -> argparse.ArgumentParser:
                         "num_updates), updated inside the SGD kernel, saved "
                         "in the checkpoint as flat_ema and used by "
                         "--eval_every_steps; 0 = off")
+    p.add_argument("--clip_grad_norm", type=_clip, default=0.0, metavar="C",
+                   help="C > 0: scale the aggregated (averaged) gradient by "
+                        "min(1, C / (global L2 norm + 1e-6)) before the "
+                        "update, torch.nn.utils.clip_grad_norm_ semantics; "
+                        "the norms are reduced on the device in a fixed "
+                        "order (no host round trip, same bits on every "
+                        "rank). inf never clips and only reports the norms; "
+                        "0 = off")
     p.add_argument("--deterministic", action="store_true",
                    help="bitwise-reproducible gradients on the GPU: the fused "
                         "LeNet step reduces every weight and bias gradient "
