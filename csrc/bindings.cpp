@@ -1330,7 +1330,7 @@ void grad_mask(torch::Tensor g, double keep, int64_t seed, int64_t step,
                    cur_stream());
 }
 
-// Argument checks shared by the three gathers of the device-resident uint8
+// Argument checks shared by the four gathers of the device-resident uint8
 // set.  `op` prefixes every message; `pos` names the host position argument
 // ("step" / "start") whose device form is `pos_dev`.  A batch drawn from the
 // epoch permutation needs B <= N; a sequential chunk may run past N (the rows
@@ -1409,6 +1409,39 @@ void batch_gather_aug(torch::Tensor img_u8, torch::Tensor lab_u8,
                           bf16_mut(x), y.data_ptr<long>(), (uint32_t)a.N,
                           (uint32_t)a.B, (uint64_t)seed, (uint64_t)step, a.sd,
                           cur_stream());
+}
+
+void batch_gather_elastic(torch::Tensor img_u8, torch::Tensor lab_u8,
+                          torch::Tensor lut, torch::Tensor table,
+                          torch::Tensor taps, int64_t alpha_q,
+                          torch::Tensor x, torch::Tensor y, int64_t seed,
+                          int64_t step,
+                          c10::optional<torch::Tensor> step_dev) {
+  CHECK_CUDA(table); CHECK_CONTIG(table);
+  TORCH_CHECK(table.scalar_type() == at::kInt && table.dim() == 2 &&
+              table.size(1) == 6 && table.size(0) >= 1 &&
+              table.size(0) < (int64_t(1) << 31),
+              "batch_gather_elastic: table must be int32 [T >= 1, 6]");
+  CHECK_CUDA(taps); CHECK_CONTIG(taps);
+  TORCH_CHECK(taps.scalar_type() == at::kInt && taps.dim() == 1 &&
+              taps.size(0) == 32,
+              "batch_gather_elastic: taps must be int32 [32]");
+  TORCH_CHECK(taps.device() == img_u8.device() &&
+              table.device() == img_u8.device(),
+              "batch_gather_elastic: table and taps must be on the images' "
+              "device");
+  TORCH_CHECK(alpha_q >= 0 && alpha_q <= 16384,
+              "batch_gather_elastic: alpha_q ", alpha_q,
+              " outside [0, 16384]");
+  GatherArgs a = check_gather("batch_gather_elastic", img_u8, lab_u8, lut, x,
+                              y, "step", step, step_dev, false);
+  launch_batch_gather_elastic(img_u8.data_ptr<uint8_t>(),
+                              lab_u8.data_ptr<uint8_t>(), bf16_ptr(lut),
+                              table.data_ptr<int>(), (uint32_t)table.size(0),
+                              taps.data_ptr<int>(), (uint32_t)alpha_q,
+                              bf16_mut(x), y.data_ptr<long>(), (uint32_t)a.N,
+                              (uint32_t)a.B, (uint64_t)seed, (uint64_t)step,
+                              a.sd, cur_stream());
 }
 
 void range_gather(torch::Tensor img_u8, torch::Tensor lab_u8,
@@ -1643,6 +1676,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("img_u8"), py::arg("lab_u8"), py::arg("lut"),
         py::arg("table"), py::arg("x"), py::arg("y"), py::arg("seed"),
         py::arg("step"), py::arg("step_dev") = c10::nullopt);
+  m.def("batch_gather_elastic", &batch_gather_elastic,
+        "batch_gather_aug plus elastic distortion: the displacement field of "
+        "cpu_ref.elastic_displacement (int8 noise of elastic_key(seed, step, "
+        "j), smoothed by the int32 [32] device taps on the integer MFMA, "
+        "scaled by alpha_q = rint(256 * alpha px) in [0, 16384]) is added to "
+        "the affine source position; alpha_q = 0 is batch_gather_aug",
+        py::arg("img_u8"), py::arg("lab_u8"), py::arg("lut"),
+        py::arg("table"), py::arg("taps"), py::arg("alpha_q"), py::arg("x"),
+        py::arg("y"), py::arg("seed"), py::arg("step"),
+        py::arg("step_dev") = c10::nullopt);
   m.def("range_gather", &range_gather,
         "sequential chunk [start, start+B) of the device-resident uint8 set "
         "(LUT-normalised to bf16) into x [B,28,28,1] bf16 / y [B] int64; "

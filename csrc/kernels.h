@@ -191,6 +191,19 @@ void launch_batch_gather_aug(const uint8_t* img, const uint8_t* lab,
                              uint32_t N, uint32_t B, uint64_t seed,
                              uint64_t step, const long* step_dev,
                              hipStream_t);
+// elastic_gather.hip — batch_gather_aug plus an elastic distortion: the
+// per-image displacement field of cpu_ref.elastic_displacement (int8 noise
+// smoothed by the int32 [32] Gaussian `taps` on the integer MFMA, scaled by
+// alpha_q = rint(256 * alpha px)) is added to the affine source position.
+// Memory-safe for any table / taps / alpha_q content; alpha_q = 0 is
+// batch_gather_aug bit for bit.
+void launch_batch_gather_elastic(const uint8_t* img, const uint8_t* lab,
+                                 const unsigned short* lut, const int* table,
+                                 uint32_t T, const int* taps,
+                                 uint32_t alpha_q, unsigned short* x, long* y,
+                                 uint32_t N, uint32_t B, uint64_t seed,
+                                 uint64_t step, const long* step_dev,
+                                 hipStream_t);
 // eval_ops.hip — device-side evaluation.  range_gather: the sequential chunk
 // [start, start+B) of the resident set (start from the host or *start_dev),
 // rows past N zero-filled with label -1.  softmax_eval: loss / live / correct

@@ -30,7 +30,8 @@ import numpy as np
 import torch
 
 from ..ops import functional as Fx
-from ..ops.cpu_ref import augment_table
+from ..ops.cpu_ref import (AUG_IDENTITY, augment_table, elastic_alpha_q,
+                           elastic_taps)
 from .mnist_data import (IMAGE_SIZE, NUM_CHANNELS, PIXEL_DEPTH, TEST_IMAGES,
                          TEST_LABELS, TRAIN_IMAGES, TRAIN_LABELS,
                          extract_images_u8, extract_labels)
@@ -53,6 +54,9 @@ class DeviceDataSet:
     Augmentation: any of augment_shift (px) / augment_rotate (deg) /
     augment_scale (frac) above 0 builds a table of augment_table_size
     transforms from `seed`; a ready int32 [T,6] `aug_table` takes precedence.
+    augment_elastic (alpha, px, <= 64) above 0 adds an elastic distortion
+    whose field is smoothed by a Gaussian of augment_elastic_sigma (in
+    [1, 16]) pixels; alone it runs over a one-row identity table.
     """
 
     def __init__(self, images_u8, labels_u8, worker_id: int = 0,
@@ -60,7 +64,8 @@ class DeviceDataSet:
                  device="cpu", dtype: torch.dtype = torch.float32,
                  augment_shift: float = 0.0, augment_rotate: float = 0.0,
                  augment_scale: float = 0.0, augment_table_size: int = 4096,
-                 aug_table=None):
+                 aug_table=None, augment_elastic: float = 0.0,
+                 augment_elastic_sigma: float = 4.0):
         images_u8 = np.asarray(images_u8)
         labels_u8 = np.asarray(labels_u8)
         if images_u8.dtype != np.uint8:
@@ -87,6 +92,17 @@ class DeviceDataSet:
             aug_table = augment_table(augment_table_size, self.seed,
                                       augment_shift, augment_rotate,
                                       augment_scale)
+        # taps and alpha are built and validated on the host, then uploaded
+        self._elastic = None
+        if not float(augment_elastic) >= 0.0:  # NaN fails the compare
+            raise ValueError(f"augment_elastic={augment_elastic} must be "
+                             "in [0, 64]")
+        if augment_elastic > 0:
+            self._elastic = (
+                torch.from_numpy(elastic_taps(augment_elastic_sigma))
+                .to(self.device), elastic_alpha_q(augment_elastic))
+            if aug_table is None:
+                aug_table = np.array([AUG_IDENTITY], dtype=np.int32)
         self._aug_table = None
         if aug_table is not None:
             tab = torch.as_tensor(np.asarray(aug_table))
@@ -99,6 +115,11 @@ class DeviceDataSet:
     def aug_table(self):
         """int32 [T,6] on the device, or None when augmentation is off."""
         return self._aug_table
+
+    @property
+    def elastic(self):
+        """(int32 [32] taps on the device, alpha_q), or None when off."""
+        return self._elastic
 
     @property
     def images(self):
@@ -121,12 +142,14 @@ class DeviceDataSet:
                     step_dev=None, augment: bool = True):
         """Write the batch at `step` (host int) or `*step_dev` (device
         int64; capturable into a hipGraph) into x [B,28,28,1] / y [B],
-        augmented when the data set has a table (augment=False: raw)."""
+        augmented when the data set has a table and / or an elastic field
+        (augment=False: raw)."""
         if x.dtype != self.dtype:
             raise TypeError(f"x is {x.dtype}, data set built for {self.dtype}")
         return Fx.batch_gather(self._images, self._labels, self._lut, x, y,
                                self.seed, step=step, step_dev=step_dev,
-                               aug_table=self._aug_table if augment else None)
+                               aug_table=self._aug_table if augment else None,
+                               elastic=self._elastic if augment else None)
 
     def range_into(self, x: torch.Tensor, y: torch.Tensor, start=None,
                    start_dev=None):

@@ -698,9 +698,13 @@ def make_dataset(flags, rank: int, world: int, device, dtype):
     if min(augment.values()) < 0:
         raise ValueError(f"augmentation magnitudes must be >= 0: {augment}")
     augmented = max(augment.values()) > 0
-    if augmented and not device_data:
+    elastic = getattr(flags, "augment_elastic", 0) or 0
+    if not 0 <= elastic <= 64:  # NaN fails both compares
+        raise ValueError(f"--augment_elastic {elastic} outside [0, 64]")
+    if (augmented or elastic > 0) and not device_data:
         raise ValueError(
-            "--augment_shift/--augment_rotate/--augment_scale need an "
+            "--augment_shift/--augment_rotate/--augment_scale/"
+            "--augment_elastic need an "
             "effective --device_data (idx-gz files, not --synthetic_data / "
             "--fake_data): augmentation runs inside the resident gather and "
             "the host-fed and synthetic paths have none")
@@ -711,6 +715,10 @@ def make_dataset(flags, rank: int, world: int, device, dtype):
                 getattr(flags, "augment_table", 0) or 4096
         else:
             augment = {}
+        if elastic > 0:
+            augment["augment_elastic"] = elastic
+            augment["augment_elastic_sigma"] = \
+                getattr(flags, "augment_elastic_sigma", 0) or 4.0
         return load_device_mnist(flags.data_dir, subset=flags.subset,
                                  worker_id=rank, n_workers=world,
                                  shard=not flags.no_shard,

@@ -434,19 +434,23 @@ def aug_indices(T: int, seed: int, step: int, b: int):
     return (r % np.uint64(T)).astype(np.int64)
 
 
-def affine_warp_u8(rows_u8, entries):
-    """Integer bilinear warp of uint8 images.  rows_u8: [b, 784] uint8,
-    entries: [b, 6] integer (one table row per image) -> uint8 [b, 784].
-    Defined for entries within the builder's bounds (int64 here; the kernel's
-    int32 arithmetic agrees there)."""
-    b = rows_u8.shape[0]
-    dev = rows_u8.device
+def _affine_coords(entries, b, dev):
+    """Q17 source coordinates (SX, SY), int64 [b, 28, 28], of every output
+    pixel under one table row per image."""
     e = entries.to(device=dev, dtype=torch.int64).view(b, 6, 1, 1)
     u = 2 * torch.arange(_SIDE, device=dev, dtype=torch.int64) - (_SIDE - 1)
     uc, ur = u.view(1, 1, _SIDE), u.view(1, _SIDE, 1)
     half = (_SIDE - 1) * AUG_ONE
     SX = half + e[:, 0] * uc + e[:, 1] * ur + 2 * e[:, 4]
     SY = half + e[:, 2] * uc + e[:, 3] * ur + 2 * e[:, 5]
+    return SX, SY
+
+
+def _bilinear_u8(rows_u8, SX, SY):
+    """The part of the warp after the coordinates: x0/y0/fx/fy split of the
+    Q17 positions, four predicated taps (background 0), 8-bit weights,
+    round to nearest.  Shared by affine_warp_u8 and elastic_warp_u8."""
+    b = rows_u8.shape[0]
     x0, y0 = SX >> 17, SY >> 17  # arithmetic shift = floor
     fx, fy = (SX >> 9) & 255, (SY >> 9) & 255
     src = rows_u8.reshape(b, _SIDE * _SIDE).long()
@@ -463,22 +467,179 @@ def affine_warp_u8(rows_u8, entries):
     return v.to(torch.uint8).view(b, _SIDE * _SIDE)
 
 
+def affine_warp_u8(rows_u8, entries):
+    """Integer bilinear warp of uint8 images.  rows_u8: [b, 784] uint8,
+    entries: [b, 6] integer (one table row per image) -> uint8 [b, 784].
+    Defined for entries within the builder's bounds (int64 here; the kernel's
+    int32 arithmetic agrees there)."""
+    SX, SY = _affine_coords(entries, rows_u8.shape[0], rows_u8.device)
+    return _bilinear_u8(rows_u8, SX, SY)
+
+
+# -- elastic distortion (integer only; csrc/elastic_gather.hip mirrors it) ---
+#
+# Simard et al. 2003: per image and axis a field of uniform noise, smoothed
+# by a Gaussian, scaled by alpha, added to the source position of every
+# output pixel.  Here the noise is int8, the Gaussian a separable integer
+# Toeplitz matrix G (taps summing to <= 256, zero outside the image, no
+# renormalisation: the field tapers at the border), and both smoothing passes
+# are exact integer matrix products, so any summation order gives the same
+# bits.  Flat pixel p = r * 28 + c; axis 0 displaces x (columns), 1 y (rows).
+
+ELASTIC_KEY_ADD = 0x3C6EF372    # separates the field key from aug_indices
+ELASTIC_NOISE_MUL = 0xB5297A4D  # odd: element index -> hash input stride
+ELASTIC_MAX_ALPHA = 64.0        # px; A = rint(256 alpha) <= 16384
+ELASTIC_MAX_A = 16384
+
+
+def elastic_key(seed: int, step: int, j):
+    """32-bit field key of batch position(s) j at `step` -> uint64 numpy
+    array (values < 2^32) shaped like j.  The (base, step lo, step hi, j)
+    chain of aug_indices under another additive constant: independent of the
+    table row choice, full 64-bit step, keyed on the batch POSITION."""
+    import numpy as np
+    step = int(step)
+    if step < 0:
+        raise ValueError("step must be >= 0")
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    base = _mix32((seed & _M32) ^ _mix32(((seed >> 32) + 0x9E3779B9) & _M32))
+    lo, hi = step & _M32, (step >> 32) & _M32
+    k = _mix32((base + ELASTIC_KEY_ADD + lo * 0x9E3779B1) & _M32)
+    k = _mix32(k ^ _mix32((hi + 0x7F4A7C15) & _M32))
+    j = np.asarray(j, dtype=np.uint64)
+    return _mix32((np.uint64(k) + j * np.uint64(0x85EBCA6B)) & np.uint64(_M32))
+
+
+def elastic_noise(keys):
+    """int8-valued noise n[a][p] = (mix32(key + (a*784 + p) * C) >> 24) - 128
+    in [-128, 127] -> int64 numpy [b, 2, 28, 28] for uint64 keys [b]."""
+    import numpy as np
+    keys = np.asarray(keys, dtype=np.uint64).reshape(-1, 1)
+    e = np.arange(2 * _SIDE * _SIDE, dtype=np.uint64).reshape(1, -1)
+    m = _mix32((keys + e * np.uint64(ELASTIC_NOISE_MUL)) & np.uint64(_M32))
+    n = (m >> np.uint64(24)).astype(np.int64) - 128
+    return n.reshape(-1, 2, _SIDE, _SIDE)
+
+
+def check_elastic_taps(taps):
+    """The bounds the integer field rests on: 32 non-negative taps, each
+    <= 127 (an int8 operand), g[0] + 2 * sum(g[1:]) <= 256, nothing past
+    distance 27.  -> int32 numpy [32]."""
+    import numpy as np
+    g = np.asarray(taps)
+    if g.shape != (32,) or g.dtype.kind not in "iu":
+        raise ValueError("elastic taps must be 32 integers")
+    g = g.astype(np.int64)
+    if g.min() < 0 or g.max() > 127 or g[_SIDE:].any() \
+            or g[0] + 2 * g[1:].sum() > 256:
+        raise ValueError("elastic taps must be in [0, 127], zero past "
+                         "distance 27, with weighted sum <= 256")
+    return g.astype(np.int32)
+
+
+def elastic_taps(sigma: float):
+    """Integer Gaussian taps -> int32 numpy [32]: R = min(27, ceil(3 sigma)),
+    g[d] = rint(256 exp(-d^2 / 2 sigma^2) / Z) for d <= R with Z the sum over
+    -R..R, zero beyond; g[0] is then decremented until g[0] + 2 sum_{d>=1}
+    g[d] <= 256.  sigma in [1, 16] (below about 0.81 the centre tap would
+    pass 127, the int8 operand bound); NaN fails the range check."""
+    import numpy as np
+    sigma = float(sigma)
+    if not (1.0 <= sigma <= 16.0):  # NaN fails both compares
+        raise ValueError(f"elastic_taps: sigma={sigma} outside [1, 16]")
+    R = min(_SIDE - 1, int(np.ceil(3.0 * sigma)))
+    d = np.arange(R + 1, dtype=np.float64)
+    w = np.exp(-d * d / (2.0 * sigma * sigma))
+    g = np.zeros(32, dtype=np.int64)
+    g[:R + 1] = np.rint(256.0 * w / (w[0] + 2.0 * w[1:].sum()))
+    while g[0] + 2 * g[1:].sum() > 256:
+        g[0] -= 1
+    return check_elastic_taps(g)
+
+
+def elastic_alpha_q(alpha: float) -> int:
+    """A = rint(alpha * 256) for alpha in pixels, 0 < alpha <= 64."""
+    alpha = float(alpha)
+    if not (0.0 < alpha <= ELASTIC_MAX_ALPHA):  # NaN fails both compares
+        raise ValueError(f"elastic alpha={alpha} outside (0, 64] pixels")
+    return int(round(alpha * 256.0))
+
+
+def elastic_field(taps, noise):
+    """Smoothed integer field of int8-valued noise [..., 28, 28] ->
+    (F, T8), both int64 numpy of the same shape.  G[i][k] = g[|i-k|]:
+
+      T  = G . N            |T| <= 256 * 128
+      T8 = (T + 128) >> 8   arithmetic shift; in [-128, 127]: the extremes
+                            are T = 256 * 127 = 32512 -> 32640 >> 8 = 127
+                            and T = -256 * 128 = -32768 -> -32640 >> 8 = -128
+      F  = T8 . G^T         |F| <= 128 * 256 = 32768
+
+    F / 32768 is the smoothed field in units of the uniform(-1, 1) noise."""
+    import numpy as np
+    g = check_elastic_taps(taps).astype(np.int64)
+    i = np.arange(_SIDE)
+    G = g[np.abs(i[:, None] - i[None, :])]
+    n = np.asarray(noise, dtype=np.int64)
+    assert n.min() >= -128 and n.max() <= 127
+    T8 = (G @ n + 128) >> 8
+    assert T8.min() >= -128 and T8.max() <= 127
+    F = T8 @ G.T
+    assert np.abs(F).max() <= 32768
+    return F, T8
+
+
+def elastic_displacement(taps, alpha_q: int, seed: int, step: int, b: int):
+    """dS[j][a][p] = (A * F[a][p]) >> 6 (arithmetic shift; |A * F| <= 2^29)
+    for batch positions j < b -> int64 numpy [b, 2, 28, 28]: the
+    displacement in the Q17 units of affine_warp_u8's SX / SY.  |dS| <= 2^23
+    (64 px), so next to |a| <= 4, |t| <= 64 px (|SX| < 2^25) the sum stays
+    far inside int32."""
+    import numpy as np
+    A = int(alpha_q)
+    if not 0 <= A <= ELASTIC_MAX_A:
+        raise ValueError(f"elastic alpha_q={A} outside [0, {ELASTIC_MAX_A}]")
+    keys = elastic_key(seed, step, np.arange(int(b)))
+    F, _ = elastic_field(taps, elastic_noise(keys))
+    return (A * F) >> 6
+
+
+def elastic_warp_u8(rows_u8, entries, dS):
+    """affine_warp_u8 with SX + dS[:, 0] and SY + dS[:, 1] per output pixel
+    (dS: integer [b, 2, 28, 28]); all-zero dS is affine_warp_u8."""
+    b, dev = rows_u8.shape[0], rows_u8.device
+    SX, SY = _affine_coords(entries, b, dev)
+    d = torch.as_tensor(dS).to(device=dev, dtype=torch.int64)
+    return _bilinear_u8(rows_u8, SX + d[:, 0], SY + d[:, 1])
+
+
 def batch_gather(img_u8, lab_u8, lut, x, y, seed: int, step: int,
-                 aug_table=None):
+                 aug_table=None, elastic=None):
     """x[j] = lut[img_u8[idx[j]]], y[j] = lab_u8[idx[j]] written into the
     caller's buffers (any device; x takes lut's dtype).  With `aug_table`
     (int32 [T, 6]) row j is warped by table entry aug_indices(...)[j]
-    between the permutation and the LUT; labels are unchanged."""
+    between the permutation and the LUT; labels are unchanged.  With
+    `elastic` = (taps int [32], A) the warp also adds the displacement field
+    of elastic_key(seed, step, j); without a table the affine part is the
+    identity."""
     n, b = lab_u8.shape[0], y.shape[0]
     idx = torch.from_numpy(batch_indices(n, b, seed, step)).to(img_u8.device)
     rows = img_u8[idx]
+    if aug_table is None and elastic is not None:
+        aug_table = torch.tensor([AUG_IDENTITY], dtype=torch.int32)
     if aug_table is not None:
         if aug_table.dim() != 2 or aug_table.shape[1] != 6 \
                 or aug_table.shape[0] < 1:
             raise ValueError("aug_table must be [T >= 1, 6]")
         t = torch.from_numpy(aug_indices(aug_table.shape[0], seed, step, b))
-        rows = affine_warp_u8(rows.reshape(b, -1),
-                              aug_table[t.to(aug_table.device)])
+        ent = aug_table[t.to(aug_table.device)]
+        if elastic is None:
+            rows = affine_warp_u8(rows.reshape(b, -1), ent)
+        else:
+            taps, A = elastic
+            taps = torch.as_tensor(taps).cpu().numpy()
+            dS = elastic_displacement(taps, A, seed, step, b)
+            rows = elastic_warp_u8(rows.reshape(b, -1), ent, dS)
     x.copy_(lut[rows.long()].reshape(x.shape))
     y.copy_(lab_u8[idx].long())
     return x, y

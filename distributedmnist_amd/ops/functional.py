@@ -192,10 +192,22 @@ def grad_mask(grad: torch.Tensor, keep: float, seed: int, step: int,
         grad.mul_(mask.to(grad.device))
 
 
+_IDENTITY_TABLES: dict = {}
+
+
+def _identity_table(device) -> torch.Tensor:
+    """One-row identity transform table, uploaded once per device (a call
+    under hipGraph capture must not copy from the host)."""
+    if device not in _IDENTITY_TABLES:
+        _IDENTITY_TABLES[device] = torch.tensor(
+            [cpu_ref.AUG_IDENTITY], dtype=torch.int32, device=device)
+    return _IDENTITY_TABLES[device]
+
+
 def batch_gather(img_u8: torch.Tensor, lab_u8: torch.Tensor,
                  lut: torch.Tensor, x: torch.Tensor, y: torch.Tensor,
                  seed: int, step: int | None = None, step_dev=None,
-                 aug_table: torch.Tensor | None = None):
+                 aug_table: torch.Tensor | None = None, elastic=None):
     """Build the batch at `step` from the resident uint8 training set into
     the caller's buffers: x[j] = lut[img[perm(...)]] ([B,28,28,1], lut's
     dtype), y[j] = labels ([B] int64).  The sample order is a pure function
@@ -204,7 +216,11 @@ def batch_gather(img_u8: torch.Tensor, lab_u8: torch.Tensor,
     path) is given.  With `aug_table` (int32 [T,6], ops/cpu_ref.py::
     augment_table) image j is warped by table row aug_indices(seed, step, j)
     before the LUT (batch_gather_aug_kernel on the HIP path); without it the
-    plain kernel runs."""
+    plain kernel runs.  With `elastic` = (taps int32 [32], alpha_q) the
+    displacement field of ops/cpu_ref.py::elastic_displacement is added to
+    the warp (batch_gather_elastic_kernel on the HIP path), over a one-row
+    identity table when no `aug_table` is given (cached per device after the
+    first call; pass a table when the first call is captured)."""
     if (step is None) == (step_dev is None):
         raise ValueError("batch_gather: pass exactly one of step / step_dev")
     if y.shape[0] > lab_u8.shape[0]:
@@ -214,11 +230,24 @@ def batch_gather(img_u8: torch.Tensor, lab_u8: torch.Tensor,
             aug_table.dtype != torch.int32 or aug_table.dim() != 2
             or aug_table.shape[1] != 6 or aug_table.shape[0] < 1):
         raise ValueError("batch_gather: aug_table must be int32 [T >= 1, 6]")
+    if elastic is not None:
+        taps, alpha_q = elastic
+        if taps.dtype != torch.int32 or tuple(taps.shape) != (32,):
+            raise ValueError("batch_gather: elastic taps must be int32 [32]")
+        if not 0 <= int(alpha_q) <= cpu_ref.ELASTIC_MAX_A:
+            raise ValueError(f"batch_gather: elastic alpha_q {alpha_q} "
+                             f"outside [0, {cpu_ref.ELASTIC_MAX_A}]")
+        if aug_table is None:
+            aug_table = _identity_table(x.device)
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     if _use_hip(x):
         if seed >= 1 << 63:
             seed -= 1 << 64  # int64 carrier of the same 64 bits
-        if aug_table is None:
+        if elastic is not None:
+            _C.ext().batch_gather_elastic(
+                img_u8, lab_u8, lut, aug_table, taps, int(alpha_q), x, y,
+                seed, 0 if step is None else int(step), step_dev=step_dev)
+        elif aug_table is None:
             _C.ext().batch_gather(img_u8, lab_u8, lut, x, y, seed,
                                   0 if step is None else int(step),
                                   step_dev=step_dev)
@@ -230,7 +259,7 @@ def batch_gather(img_u8: torch.Tensor, lab_u8: torch.Tensor,
         if step is None:
             step = int(step_dev.item())  # reference path: host sync is fine
         cpu_ref.batch_gather(img_u8, lab_u8, lut, x, y, seed, int(step),
-                             aug_table=aug_table)
+                             aug_table=aug_table, elastic=elastic)
     return x, y
 
 

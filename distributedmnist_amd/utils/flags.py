@@ -38,6 +38,20 @@ def _clip(text: str) -> float:
     return v
 
 
+def _in_range(lo: float, hi: float):
+    """argparse type: a float in [lo, hi]."""
+    def parse(text: str) -> float:
+        try:
+            v = float(text)
+        except ValueError:
+            raise argparse.ArgumentTypeError(f"not a number: {text!r}")
+        if not lo <= v <= hi:  # also refuses nan
+            raise argparse.ArgumentTypeError(
+                f"must lie in [{lo:g}, {hi:g}], got {text}")
+        return v
+    return parse
+
+
 def build_train_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="MI355X-native distributed MNIST training")
     # --- reference-compatible flags (distributed_train.py:36-99) ---
@@ -130,6 +144,18 @@ def build_train_parser() -> argparse.ArgumentParser:
     p.add_argument("--augment_table", type=int, default=4096, metavar="T",
                    help="number of distinct random transforms the augmented "
                         "gather draws from (built once per rank)")
+    p.add_argument("--augment_elastic", type=_in_range(0.0, 64.0),
+                   default=0.0, metavar="ALPHA",
+                   help=">0 (with --device_data): elastic distortion (Simard "
+                        "et al. 2003) of every training image inside the "
+                        "resident gather: a random displacement field of up "
+                        "to ALPHA pixels (<= 64), smoothed by a Gaussian; a "
+                        "pure function of (seed, rank, step, batch position). "
+                        "Combines with the affine flags; 0 = off")
+    p.add_argument("--augment_elastic_sigma", type=_in_range(1.0, 16.0),
+                   default=4.0, metavar="S",
+                   help="standard deviation in pixels, in [1, 16], of the "
+                        "Gaussian that smooths the elastic field")
     p.add_argument("--eval_every_steps", type=int, default=0,
                    help=">0: keep the test set on the device and evaluate it "
                         "every N steps (and after the last step); the step "

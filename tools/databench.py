@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Real-data input-pipeline benchmark (bench.py measures --synthetic_data
 only).  Generates MNIST-sized idx-gz files from a seed, then times one
-LeNet training step fed five ways, per batch size:
+LeNet training step fed six ways, per batch size:
 
   a  host    DataSet.next_batch -> Trainer.to_device -> graph_or_eager_step
   b  eager   --device_data --hip_graph off  (resident_step, eager gather)
@@ -9,6 +9,8 @@ LeNet training step fed five ways, per batch size:
   d  synth   --synthetic_data               (graph; device slices + 2 copies)
   e  augment --device_data --augment_shift 2 --augment_rotate 10
              --augment_scale 0.1            (graph; warped gather captured)
+  f  elastic e's flags + --augment_elastic 34 --augment_elastic_sigma 4
+                                            (graph; elastic gather captured)
 
 Every variant is warmed up at its shape, then timed over `--steps` steps
 between two device events with ONE synchronise at the end and no per-step
@@ -36,6 +38,9 @@ VARIANTS = {
           ["--device_data", "--augment_shift", "2", "--augment_rotate", "10",
            "--augment_scale", "0.1"]),
 }
+VARIANTS["f"] = ("device_data_elastic_graph",
+                 VARIANTS["e"][1] + ["--augment_elastic", "34",
+                                     "--augment_elastic_sigma", "4"])
 
 
 def build_variant(key, data_dir, train_dir, batch_size, seed):
@@ -87,7 +92,7 @@ def spread(xs):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--batch_sizes", default="64,1024")
-    ap.add_argument("--variants", default="a,b,c,d,e")
+    ap.add_argument("--variants", default="a,b,c,d,e,f")
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=5)
@@ -132,7 +137,8 @@ def main():
                     ips[k].append(round(
                         bs * args.steps / timed(steps_fn[k], args.steps), 1))
             entry = {k: dict(spread(v), runs=v) for k, v in ips.items()}
-            for num, den in (("c", "a"), ("c", "d"), ("e", "c")):
+            for num, den in (("c", "a"), ("c", "d"), ("e", "c"),
+                             ("f", "e")):
                 if num in ips and den in ips:
                     entry[f"{num}/{den}"] = spread(
                         [round(x / y, 4) for x, y in zip(ips[num], ips[den])])
