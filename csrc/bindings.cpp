@@ -1138,22 +1138,73 @@ static const float* clip_coef_ptr(const c10::optional<torch::Tensor>& coef,
   return coef->data_ptr<float>();
 }
 
+// (offset, numel) pairs -> the by-value segment table of grad_norm /
+// lars_norm / the LARS SGD pass: 1 to GRAD_NORM_MAX_SEGS segments that tile
+// [0, n) in order
+static GradNormSegs tiling_segs(const char* who,
+                                const std::vector<int64_t>& offsets,
+                                const std::vector<int64_t>& numels,
+                                int64_t n) {
+  const size_t ns = offsets.size();
+  TORCH_CHECK(ns >= 1 && ns <= GRAD_NORM_MAX_SEGS && numels.size() == ns,
+              who, ": 1 to ", GRAD_NORM_MAX_SEGS,
+              " segments, one length per offset");
+  GradNormSegs segs{};
+  int64_t at = 0;
+  for (size_t i = 0; i < ns; ++i) {
+    TORCH_CHECK(offsets[i] == at && numels[i] >= 0,
+                who, ": the segments must tile [0, n) in order");
+    segs.off[i] = offsets[i];
+    segs.len[i] = numels[i];
+    at += numels[i];
+  }
+  TORCH_CHECK(at == n, who, ": the segments must tile [0, n) in order");
+  segs.n = (int)ns;
+  return segs;
+}
+
+// optional LARS table of the SGD pass (lars_norm's lars_tab, read on the
+// device) with its segment table: nullptr = the pass without LARS
+static const float* lars_tab_ptr(const c10::optional<torch::Tensor>& tab,
+                                 const c10::optional<torch::Tensor>& clip_coef,
+                                 const std::vector<int64_t>& offsets,
+                                 const std::vector<int64_t>& numels,
+                                 const torch::Tensor& master,
+                                 GradNormSegs* segs) {
+  if (!tab.has_value() || !tab->defined()) return nullptr;
+  TORCH_CHECK(!(clip_coef.has_value() && clip_coef->defined()),
+              "sgd_step: lars_tab and clip_coef are mutually exclusive (the "
+              "table holds the clip coefficient already)");
+  CHECK_CUDA((*tab)); CHECK_F32((*tab)); CHECK_CONTIG((*tab));
+  TORCH_CHECK(tab->numel() == 2 * GRAD_NORM_MAX_SEGS &&
+              tab->get_device() == master.get_device(),
+              "sgd_step: lars_tab holds ", 2 * GRAD_NORM_MAX_SEGS,
+              " fp32 values on master's device");
+  *segs = tiling_segs("sgd_step", offsets, numels, master.numel());
+  return tab->data_ptr<float>();
+}
+
 void sgd_step(torch::Tensor master, torch::Tensor grad, torch::Tensor shadow,
               bool has_shadow, double lr, double scale, double dc_keep,
               int64_t seed, int64_t offset,
               c10::optional<torch::Tensor> momentum, double mu,
               c10::optional<torch::Tensor> ema, double ema_decay,
-              c10::optional<torch::Tensor> clip_coef) {
+              c10::optional<torch::Tensor> clip_coef,
+              c10::optional<torch::Tensor> lars_tab,
+              std::vector<int64_t> offsets, std::vector<int64_t> numels) {
   CHECK_CUDA(master); CHECK_F32(master); CHECK_CONTIG(master);
   CHECK_F32(grad); CHECK_CONTIG(grad);
   float* mom = momentum_ptr(momentum);
   float* emap = ema_ptr(ema, master, ema_decay);
+  GradNormSegs segs{};
+  const float* tab = lars_tab_ptr(lars_tab, clip_coef, offsets, numels, master,
+                                  &segs);
   launch_sgd_step(master.data_ptr<float>(), grad.data_ptr<float>(),
                   has_shadow ? bf16_mut(shadow) : nullptr,
                   has_shadow ? 1 : 0, master.numel(),
                   (float)(lr * scale), (float)dc_keep, (uint64_t)seed,
                   (uint64_t)offset, mom, (float)mu, emap, (float)ema_decay,
-                  clip_coef_ptr(clip_coef, master), cur_stream());
+                  clip_coef_ptr(clip_coef, master), tab, &segs, cur_stream());
 }
 
 void sgd_step_dev(torch::Tensor master, torch::Tensor grad,
@@ -1162,10 +1213,15 @@ void sgd_step_dev(torch::Tensor master, torch::Tensor grad,
                   torch::Tensor offset_dev,
                   c10::optional<torch::Tensor> momentum, double mu,
                   bool zero_grad, c10::optional<torch::Tensor> ema,
-                  double ema_decay, c10::optional<torch::Tensor> clip_coef) {
+                  double ema_decay, c10::optional<torch::Tensor> clip_coef,
+                  c10::optional<torch::Tensor> lars_tab,
+                  std::vector<int64_t> offsets, std::vector<int64_t> numels) {
   CHECK_CUDA(master); CHECK_F32(master); CHECK_CONTIG(master);
   CHECK_F32(grad); CHECK_CONTIG(grad);
   CHECK_F32(lr_scale_dev);
+  GradNormSegs segs{};
+  const float* tab = lars_tab_ptr(lars_tab, clip_coef, offsets, numels, master,
+                                  &segs);
   float* mom = momentum_ptr(momentum);  // same fp32 + contiguity checks
   launch_sgd_step_dev(master.data_ptr<float>(), grad.data_ptr<float>(),
                       has_shadow ? bf16_mut(shadow) : nullptr,
@@ -1174,7 +1230,8 @@ void sgd_step_dev(torch::Tensor master, torch::Tensor grad,
                       (uint64_t)seed, offset_dev.data_ptr<long>(),
                       mom, (float)mu, zero_grad ? 1 : 0,
                       ema_ptr(ema, master, ema_decay), (float)ema_decay,
-                      clip_coef_ptr(clip_coef, master), cur_stream());
+                      clip_coef_ptr(clip_coef, master), tab, &segs,
+                      cur_stream());
 }
 
 // Per-tensor and global gradient norms + the clip coefficient of the flat
@@ -1190,11 +1247,9 @@ void grad_norm(torch::Tensor grad, std::vector<int64_t> offsets,
               clipped_steps.numel() == 1,
               "grad_norm: clipped_steps is one int64");
   const int64_t n = grad.numel();
-  const size_t ns = offsets.size();
   TORCH_CHECK(n >= 1, "grad_norm: empty gradient");
-  TORCH_CHECK(ns >= 1 && ns <= GRAD_NORM_MAX_SEGS && numels.size() == ns,
-              "grad_norm: 1 to ", GRAD_NORM_MAX_SEGS,
-              " segments, one length per offset");
+  GradNormSegs segs = tiling_segs("grad_norm", offsets, numels, n);
+  const size_t ns = offsets.size();
   TORCH_CHECK(stats.numel() == (int64_t)(2 + ns),
               "grad_norm: stats holds 2 + segments values");
   TORCH_CHECK(stats.get_device() == grad.get_device() &&
@@ -1205,17 +1260,6 @@ void grad_norm(torch::Tensor grad, std::vector<int64_t> offsets,
   TORCH_CHECK(clip > 0.0, "grad_norm: clip must be > 0 (inf = never clip)");
   TORCH_CHECK(grad_scale > 0.0 && std::isfinite(grad_scale),
               "grad_norm: grad_scale must be finite and > 0");
-  GradNormSegs segs{};
-  int64_t at = 0;
-  for (size_t i = 0; i < ns; ++i) {
-    TORCH_CHECK(offsets[i] == at && numels[i] >= 0,
-                "grad_norm: the segments must tile [0, n) in order");
-    segs.off[i] = offsets[i];
-    segs.len[i] = numels[i];
-    at += numels[i];
-  }
-  TORCH_CHECK(at == n, "grad_norm: the segments must tile [0, n) in order");
-  segs.n = (int)ns;
   auto s = cur_stream();
   static auto* ws = new WorkspaceSlots(64);
   float* part = device_workspace(
@@ -1228,6 +1272,83 @@ void grad_norm(torch::Tensor grad, std::vector<int64_t> offsets,
   launch_grad_norm(grad.data_ptr<float>(), n, segs, (float)grad_scale,
                    (float)clip, stats.data_ptr<float>(),
                    clipped_steps.data_ptr<long>(), part, ticket, s);
+}
+
+// LARS trust ratios of (master, grad) per tensor, on the device (lars.hip):
+// lars_tab [2 * GRAD_NORM_MAX_SEGS] and lars_stats [3 * segments] are stored;
+// clip > 0 also stores clip_stats / bumps clipped_steps exactly as grad_norm
+// does (the caller then launches no grad_norm), clip == 0 is "no clipping".
+void lars_norm(torch::Tensor master, torch::Tensor grad,
+               std::vector<int64_t> offsets, std::vector<int64_t> numels,
+               int64_t adapt_mask, double grad_scale, double eta, double wd,
+               double clip, torch::Tensor lars_tab, torch::Tensor lars_stats,
+               c10::optional<torch::Tensor> clip_stats,
+               c10::optional<torch::Tensor> clipped_steps) {
+  CHECK_CUDA(master); CHECK_F32(master); CHECK_CONTIG(master);
+  CHECK_CUDA(grad); CHECK_F32(grad); CHECK_CONTIG(grad);
+  CHECK_CUDA(lars_tab); CHECK_F32(lars_tab); CHECK_CONTIG(lars_tab);
+  CHECK_CUDA(lars_stats); CHECK_F32(lars_stats); CHECK_CONTIG(lars_stats);
+  const int64_t n = grad.numel();
+  TORCH_CHECK(n >= 1, "lars_norm: empty gradient");
+  TORCH_CHECK(master.numel() == n,
+              "lars_norm: master and grad hold the same number of values");
+  GradNormSegs segs = tiling_segs("lars_norm", offsets, numels, n);
+  const int64_t ns = segs.n;
+  TORCH_CHECK(lars_tab.numel() == 2 * GRAD_NORM_MAX_SEGS,
+              "lars_norm: lars_tab holds ", 2 * GRAD_NORM_MAX_SEGS, " values");
+  TORCH_CHECK(lars_stats.numel() == 3 * ns,
+              "lars_norm: lars_stats holds 3 values per segment");
+  const int dev = grad.get_device();
+  TORCH_CHECK(master.get_device() == dev && lars_tab.get_device() == dev &&
+              lars_stats.get_device() == dev,
+              "lars_norm: master, lars_tab and lars_stats live on grad's "
+              "device");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(grad.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(master.data_ptr()) % 16 == 0,
+              "lars_norm: master and grad must be 16-byte aligned");
+  TORCH_CHECK(adapt_mask >= 0 && adapt_mask < (int64_t(1) << ns),
+              "lars_norm: adapt_mask has one bit per segment");
+  TORCH_CHECK(eta > 0.0 && std::isfinite(eta),
+              "lars_norm: eta must be finite and > 0");
+  TORCH_CHECK(wd >= 0.0 && std::isfinite(wd),
+              "lars_norm: wd must be finite and >= 0");
+  TORCH_CHECK(grad_scale > 0.0 && std::isfinite(grad_scale),
+              "lars_norm: grad_scale must be finite and > 0");
+  TORCH_CHECK(clip >= 0.0, "lars_norm: clip must be 0 (off) or > 0 "
+              "(inf = never clip)");
+  float* cs = nullptr;
+  long* cnt = nullptr;
+  if (clip > 0.0) {
+    TORCH_CHECK(clip_stats.has_value() && clip_stats->defined() &&
+                clipped_steps.has_value() && clipped_steps->defined(),
+                "lars_norm: clip > 0 needs clip_stats and clipped_steps");
+    CHECK_CUDA((*clip_stats)); CHECK_F32((*clip_stats));
+    CHECK_CONTIG((*clip_stats));
+    CHECK_CUDA((*clipped_steps)); CHECK_CONTIG((*clipped_steps));
+    TORCH_CHECK(clipped_steps->scalar_type() == at::kLong &&
+                clipped_steps->numel() == 1,
+                "lars_norm: clipped_steps is one int64");
+    TORCH_CHECK(clip_stats->numel() == 2 + ns,
+                "lars_norm: clip_stats holds 2 + segments values");
+    TORCH_CHECK(clip_stats->get_device() == dev &&
+                clipped_steps->get_device() == dev,
+                "lars_norm: clip_stats and clipped_steps live on grad's "
+                "device");
+    cs = clip_stats->data_ptr<float>();
+    cnt = clipped_steps->data_ptr<long>();
+  }
+  auto s = cur_stream();
+  static auto* ws = new WorkspaceSlots(64);
+  const int64_t half = GRAD_NORM_MAX_SEGS * GRAD_NORM_MAX_BLOCKS;
+  float* part = device_workspace(
+      *ws, grad, 2 * half + 1, at::kFloat, s, "lars_norm",
+      "lars_norm: first call on a device allocates its workspace and must "
+      "run outside graph capture").data_ptr<float>();
+  unsigned* ticket = reinterpret_cast<unsigned*>(part + 2 * half);
+  launch_lars_norm(master.data_ptr<float>(), grad.data_ptr<float>(), n, segs,
+                   (unsigned)adapt_mask, (float)grad_scale, (float)eta,
+                   (float)wd, (float)clip, lars_tab.data_ptr<float>(),
+                   lars_stats.data_ptr<float>(), cs, cnt, part, ticket, s);
 }
 
 void ema_publish(torch::Tensor ema, torch::Tensor shadow,
@@ -1624,7 +1745,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dc_keep"), py::arg("seed"), py::arg("offset"),
         py::arg("momentum") = c10::nullopt, py::arg("mu") = 0.0,
         py::arg("ema") = c10::nullopt, py::arg("ema_decay") = 0.0,
-        py::arg("clip_coef") = c10::nullopt);
+        py::arg("clip_coef") = c10::nullopt,
+        py::arg("lars_tab") = c10::nullopt,
+        py::arg("offsets") = std::vector<int64_t>{},
+        py::arg("numels") = std::vector<int64_t>{});
   m.def("grad_norm", &grad_norm,
         "stats[0] = grad_scale * |grad|, stats[1] = min(1, clip / (stats[0] "
         "+ 1e-6)), stats[2 + s] = grad_scale * |segment s|; clipped_steps "
@@ -1639,6 +1763,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           return std::make_tuple(blocks, chain);
         }, "(blocks, chain) of grad_norm on n elements: the grid, and the "
         "longest run of fp32 additions any element passes through");
+  m.def("lars_norm", &lars_norm,
+        "LARS: lars_tab[2t] = ratio_t * coef, lars_tab[2t + 1] = ratio_t * wd "
+        "/ grad_scale, lars_stats[3t..] = (|w_t|, coef * grad_scale * |g_t|, "
+        "ratio_t); clip > 0 also writes clip_stats / clipped_steps as "
+        "grad_norm does; one launch, no float atomics",
+        py::arg("master"), py::arg("grad"), py::arg("offsets"),
+        py::arg("numels"), py::arg("adapt_mask"), py::arg("grad_scale"),
+        py::arg("eta"), py::arg("wd"), py::arg("clip"), py::arg("lars_tab"),
+        py::arg("lars_stats"), py::arg("clip_stats") = c10::nullopt,
+        py::arg("clipped_steps") = c10::nullopt);
+  m.def("lars_norm_plan", [](int64_t n) {
+          TORCH_CHECK(n >= 1, "lars_norm_plan: n must be >= 1");
+          int blocks, chain;
+          lars_norm_plan((long)n, &blocks, &chain);
+          return std::make_tuple(blocks, chain);
+        }, "(blocks, chain) of lars_norm on n elements: grad_norm's grid; "
+        "each of the two sums is a chain of that length");
   m.def("ema_publish", &ema_publish,
         "flat fp32 parameters -> flat bf16 shadow + transposed bf16 copies "
         "of the [rows][cols] slices at `offsets`, one launch",
@@ -1653,7 +1794,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("momentum") = c10::nullopt, py::arg("mu") = 0.0,
         py::arg("zero_grad") = false,
         py::arg("ema") = c10::nullopt, py::arg("ema_decay") = 0.0,
-        py::arg("clip_coef") = c10::nullopt);
+        py::arg("clip_coef") = c10::nullopt,
+        py::arg("lars_tab") = c10::nullopt,
+        py::arg("offsets") = std::vector<int64_t>{},
+        py::arg("numels") = std::vector<int64_t>{});
   m.def("step_advance", &step_advance,
         "device-side staircase LR + step increment (inside the graph)");
   m.def("grad_mask", &grad_mask,

@@ -18,22 +18,7 @@
 // The softmax_xent_t_kernel idiom: agent-scope stores and loads of the
 // partials, __threadfence, a self-resetting ticket, a persistent workspace.
 
-#include "common.h"
-#include "kernels.h"
-
-#define GN_THREADS 256
-#define GN_WAVES (GN_THREADS / 64)
-
-// fixed shuffle tree of one wave; lane 0 holds the sum
-DEV float gn_wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
-DEV float gn_sq4(float4 g) {
-  return (g.x * g.x + g.y * g.y) + (g.z * g.z + g.w * g.w);
-}
+#include "grad_norm_common.h"
 
 extern "C" __global__ __launch_bounds__(GN_THREADS)
 void grad_norm_kernel(const float* grad, long n, GradNormSegs segs, long chunk,
@@ -51,27 +36,12 @@ void grad_norm_kernel(const float* grad, long n, GradNormSegs segs, long chunk,
     const long a = max(c0, segs.off[s]);
     const long b = min(c1, segs.off[s] + segs.len[s]);
     if (a >= b) continue;
-    // [a, a4): scalar head, [a4, b4): 16 B groups, [b4, b): scalar tail
-    long a4 = min(b, (a + 3) & ~3L);
-    long b4 = max(a4, b & ~3L);
     float acc = 0.f;
-    const long g1 = b4 >> 2;
-    // four 16 B loads per thread in flight per trip: a group past the end
-    // re-reads the range's last group (an address inside it, so the loads
-    // need no branch) and counts as zero
-    for (long g = (a4 >> 2) + tid; g < g1; g += 4 * GN_THREADS) {
-      float4 v[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        long gj = min(g + j * GN_THREADS, g1 - 1);
-        v[j] = *reinterpret_cast<const float4*>(grad + gj * 4);
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        acc += g + j * GN_THREADS < g1 ? gn_sq4(v[j]) : 0.f;
-    }
-    if (a + tid < a4) { float x = grad[a + tid]; acc += x * x; }
-    if (b4 + tid < b) { float x = grad[b4 + tid]; acc += x * x; }
+#define GN_RANGE_TWO 0
+#define GN_RANGE_SQ4 gn_sq4
+#include "grad_norm_range.inc"
+#undef GN_RANGE_TWO
+#undef GN_RANGE_SQ4
     acc = gn_wave_sum(acc);
     if (lane == 0) wred[s][wave] = acc;
   }
@@ -97,14 +67,7 @@ void grad_norm_kernel(const float* grad, long n, GradNormSegs segs, long chunk,
 
   // ---- 2. last block: per segment, the partials in block order ------------
   for (int s = 0; s < segs.n; ++s) {
-    float acc = 0.f;
-    if (segs.len[s] > 0) {
-      const long first = segs.off[s] / chunk;
-      const long lastb = (segs.off[s] + segs.len[s] - 1) / chunk;
-      for (long b = first + tid; b <= lastb; b += GN_THREADS)
-        acc += __hip_atomic_load(&part[(long)s * GRAD_NORM_MAX_BLOCKS + b],
-                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    float acc = gn_partials(part, segs.off[s], segs.len[s], s, chunk, tid);
     acc = gn_wave_sum(acc);
     if (lane == 0) wred[s][wave] = acc;
   }
@@ -125,14 +88,6 @@ void grad_norm_kernel(const float* grad, long n, GradNormSegs segs, long chunk,
   stats[1] = coef;
   if (coef < 1.f) *clipped_steps += 1;
   __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// elements per block: GRAD_NORM_CHUNK while that needs at most
-// GRAD_NORM_MAX_BLOCKS blocks, the next multiple of it above that
-static long grad_norm_chunk(long n) {
-  long per = (long)GRAD_NORM_CHUNK * GRAD_NORM_MAX_BLOCKS;
-  long k = (n + per - 1) / per;
-  return (long)GRAD_NORM_CHUNK * (k < 1 ? 1 : k);
 }
 
 void grad_norm_plan(long n, int* blocks, int* chain) {

@@ -107,6 +107,7 @@ void launch_sgd_step(float* master, float* grad, unsigned short* shadow,
                      int has_shadow, long n, float lr_scale, float dc_keep,
                      uint64_t seed, uint64_t offset, float* momentum, float mu,
                      float* ema, float ema_decay, const float* clip_coef_dev,
+                     const float* lars_tab, const struct GradNormSegs* segs,
                      hipStream_t);
 // graph-capturable variants: lr_scale / RNG offset read from device memory
 void launch_sgd_step_dev(float* master, float* grad,
@@ -115,11 +116,16 @@ void launch_sgd_step_dev(float* master, float* grad,
                          uint64_t seed, const long* offset_dev,
                          float* momentum, float mu, int zero_grad,
                          float* ema, float ema_decay,
-                         const float* clip_coef_dev, hipStream_t);
+                         const float* clip_coef_dev, const float* lars_tab,
+                         const struct GradNormSegs* segs, hipStream_t);
 // clip_coef_dev != nullptr (both launchers): the gradient is multiplied by
 // *clip_coef_dev (launch_grad_norm's stats[1]) before the drop-connect mask
 // and the momentum filter, v = mu*v + coef*g (two more instantiations;
 // nullptr launches the unchanged sgd_step_kernel / sgd_step_kernel_ema).
+// lars_tab != nullptr (both launchers, with segs, never with clip_coef_dev):
+// launch_lars_norm's device table of 2 * GRAD_NORM_MAX_SEGS floats; tensor t
+// of segs does g = tab[2t]*g, mask, g += tab[2t + 1]*w, momentum (two more
+// instantiations, sgd_step_kernel_lars / _lars_ema).
 // grad_norm.hip — per-tensor and global norms of the flat fp32 gradient and
 // the clip_grad_norm_ coefficient, one launch, no float atomics.  segs: up to
 // GRAD_NORM_MAX_SEGS (element offset, length) pairs that tile [0, n) in
@@ -143,6 +149,24 @@ struct GradNormSegs {
 void grad_norm_plan(long n, int* blocks, int* chain);
 void launch_grad_norm(const float* grad, long n, GradNormSegs segs,
                       float grad_scale, float clip, float* stats,
+                      long* clipped_steps, float* part, unsigned* ticket,
+                      hipStream_t);
+// lars.hip — LARS trust ratios: grad_norm's reduction over the gradient AND
+// the fp32 master in one launch (same segs, same grid, the gradient side bit
+// for bit grad_norm_kernel's).  adapt: bit t set = tensor t is adaptive.
+// STORED: lars_tab[2t] = ratio_t * coef, lars_tab[2t + 1] = ratio_t * wd /
+// grad_scale (0 for a tensor that is not adaptive), lars_stats[3t ..] =
+// (||w_t||, coef * grad_scale * ||g_t||, ratio_t), ratio_t = eta * wn / (gn +
+// wd * wn) for adaptive tensors with both norms > 0, else 1.  clip > 0: also
+// clip_stats / clipped_steps exactly as launch_grad_norm (coef = its
+// coefficient); clip == 0: coef = 1, both pointers unused.  part/ticket: a
+// workspace of its own, 2 * GRAD_NORM_MAX_SEGS * GRAD_NORM_MAX_BLOCKS floats
+// + the counter.
+void lars_norm_plan(long n, int* blocks, int* chain);
+void launch_lars_norm(const float* master, const float* grad, long n,
+                      GradNormSegs segs, unsigned adapt, float grad_scale,
+                      float eta, float wd, float clip, float* lars_tab,
+                      float* lars_stats, float* clip_stats,
                       long* clipped_steps, float* part, unsigned* ticket,
                       hipStream_t);
 // ema != nullptr (both launchers): the same pass also moves the fp32 moving

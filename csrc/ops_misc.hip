@@ -312,14 +312,32 @@ void softmax_xent_t_kernel(const ushort_t* logits, const long* labels,
 // by `coef` (grad_norm_kernel's clip coefficient, read once per thread by the
 // caller) first: before the drop-connect mask and before momentum,
 // v = mu*v + coef*g.  CLIP = false compiles to exactly the pass without it.
-template <bool EMA, bool CLIP = false>
+// LARS (compile-time variant, --lars_eta): every tensor t of the by-value
+// segment table has its own pair (a_t, d_t) = tab[2t], tab[2t + 1]
+// (lars_norm_kernel's table, copied into LDS by the caller; the clip
+// coefficient is already folded into a_t): g = a_t*g, then the drop-connect
+// mask, then the unmasked decay g += d_t*w, then momentum.  A 16 B group that
+// lies in one tensor (16 uniform compares for its first and for its last
+// element) takes the vector path, a group that straddles a boundary looks
+// every element up.  LARS = false compiles to exactly the pass without it.
+DEV int lars_seg_of(const GradNormSegs& segs, long idx) {
+  // the last segment that starts at or before idx (the segments tile [0, n))
+  int t = 0;
+#pragma unroll
+  for (int s = 1; s < GRAD_NORM_MAX_SEGS; ++s)
+    t += (s < segs.n && idx >= segs.off[s]) ? 1 : 0;
+  return t;
+}
+
+template <bool EMA, bool CLIP = false, bool LARS = false>
 __device__ __forceinline__
 void sgd_step_body(float* master, float* grad, ushort_t* shadow,
                    int has_shadow, long n, float lr_scale, float dc_keep,
                    uint64_t seed, uint64_t offset,
                    float* momentum, float mu, int zero_grad,
                    float* ema, float ema_decay, long i, long stride,
-                   float coef = 1.f) {
+                   float coef = 1.f, const float* tab = nullptr,
+                   const GradNormSegs* segs = nullptr) {
   // lr_scale / offset: already resolved from their device copies;
   // i / stride: the caller's grid-stride start and step, in float4 groups
   // (blockDim read in here costs a run-time workgroup-size lookup that the
@@ -336,10 +354,22 @@ void sgd_step_body(float* master, float* grad, ushort_t* shadow,
   }
   for (; i * 4 < n; i += stride) {
     long base = i * 4;
-    if (base + 3 < n) {
+    int seg = 0;
+    bool whole = true;
+    if (LARS) {
+      seg = lars_seg_of(*segs, base);
+      whole = seg == lars_seg_of(*segs, base + 3);
+    }
+    if (base + 3 < n && whole) {
       float4 g = *reinterpret_cast<const float4*>(grad + base);
       float4 m = *reinterpret_cast<const float4*>(master + base);
       if (CLIP) { g.x *= coef; g.y *= coef; g.z *= coef; g.w *= coef; }
+      float la = 1.f, ld = 0.f;
+      if (LARS) {
+        la = tab[2 * seg];
+        ld = tab[2 * seg + 1];
+        g.x *= la; g.y *= la; g.z *= la; g.w *= la;
+      }
       if (dc_keep > 0.f) {
         Philox4 ph = philox4x32(seed, offset, (uint64_t)i);
         const float s = 1.0f / 4294967296.0f;
@@ -347,6 +377,9 @@ void sgd_step_body(float* master, float* grad, ushort_t* shadow,
         g.y *= (ph.y * s < dc_keep) ? 1.f : 0.f;
         g.z *= (ph.z * s < dc_keep) ? 1.f : 0.f;
         g.w *= (ph.w * s < dc_keep) ? 1.f : 0.f;
+      }
+      if (LARS) {
+        g.x += ld * m.x; g.y += ld * m.y; g.z += ld * m.z; g.w += ld * m.w;
       }
       if (momentum) {
         float4 v = *reinterpret_cast<const float4*>(momentum + base);
@@ -374,10 +407,18 @@ void sgd_step_body(float* master, float* grad, ushort_t* shadow,
       Philox4 ph = philox4x32(seed, offset, (uint64_t)i);
       const float s = 1.0f / 4294967296.0f;
       float u[4] = {ph.x * s, ph.y * s, ph.z * s, ph.w * s};
-      for (long j = base; j < n; ++j) {
+      // LARS: also the path of a whole group that straddles a boundary
+      const long jend = LARS ? min(n, base + 4) : n;
+      for (long j = base; j < jend; ++j) {
         float g = grad[j];
         if (CLIP) g *= coef;
+        int sj = 0;
+        if (LARS) {
+          sj = lars_seg_of(*segs, j);
+          g *= tab[2 * sj];
+        }
         if (dc_keep > 0.f) g *= (u[j - base] < dc_keep) ? 1.f : 0.f;
+        if (LARS) g += tab[2 * sj + 1] * master[j];
         if (momentum) {
           float v = mu * momentum[j] + g;
           momentum[j] = v;
@@ -456,6 +497,52 @@ void sgd_step_kernel_clip_ema(float* master, float* grad, ushort_t* shadow,
                             ema, ema_decay,
                             (long)(blockIdx.x) * blockDim.x + threadIdx.x,
                             (long)gridDim.x * blockDim.x, *clip_coef_dev);
+}
+
+// the LARS instantiations: the block copies lars_norm_kernel's 32-float table
+// into LDS once; new code, built without the packed-fp32 VALU forms
+#define LARS_TARGET __attribute__((target("no-packed-fp32-ops")))
+
+extern "C" __global__ __launch_bounds__(256) LARS_TARGET
+void sgd_step_kernel_lars(float* master, float* grad, ushort_t* shadow,
+                          int has_shadow, long n, float lr_scale, float dc_keep,
+                          uint64_t seed, uint64_t offset,
+                          const float* lr_scale_dev, const long* offset_dev,
+                          float* momentum, float mu, int zero_grad,
+                          const float* lars_tab, GradNormSegs segs) {
+  __shared__ float tab[2 * GRAD_NORM_MAX_SEGS];
+  if (threadIdx.x < 2 * GRAD_NORM_MAX_SEGS)
+    tab[threadIdx.x] = lars_tab[threadIdx.x];
+  __syncthreads();
+  if (lr_scale_dev) lr_scale = *lr_scale_dev;
+  if (offset_dev) offset = (uint64_t)*offset_dev;
+  sgd_step_body<false, false, true>(
+      master, grad, shadow, has_shadow, n, lr_scale, dc_keep, seed, offset,
+      momentum, mu, zero_grad, nullptr, 0.f,
+      (long)(blockIdx.x) * blockDim.x + threadIdx.x,
+      (long)gridDim.x * blockDim.x, 1.f, tab, &segs);
+}
+
+extern "C" __global__ __launch_bounds__(256) LARS_TARGET
+void sgd_step_kernel_lars_ema(float* master, float* grad, ushort_t* shadow,
+                              int has_shadow, long n, float lr_scale,
+                              float dc_keep, uint64_t seed, uint64_t offset,
+                              const float* lr_scale_dev,
+                              const long* offset_dev, float* momentum,
+                              float mu, int zero_grad, float* ema,
+                              float ema_decay, const float* lars_tab,
+                              GradNormSegs segs) {
+  __shared__ float tab[2 * GRAD_NORM_MAX_SEGS];
+  if (threadIdx.x < 2 * GRAD_NORM_MAX_SEGS)
+    tab[threadIdx.x] = lars_tab[threadIdx.x];
+  __syncthreads();
+  if (lr_scale_dev) lr_scale = *lr_scale_dev;
+  if (offset_dev) offset = (uint64_t)*offset_dev;
+  sgd_step_body<true, false, true>(
+      master, grad, shadow, has_shadow, n, lr_scale, dc_keep, seed, offset,
+      momentum, mu, zero_grad, ema, ema_decay,
+      (long)(blockIdx.x) * blockDim.x + threadIdx.x,
+      (long)gridDim.x * blockDim.x, 1.f, tab, &segs);
 }
 
 // step/LR advance: device-side staircase LR so a captured graph needs no
@@ -604,19 +691,31 @@ void launch_softmax_xent(const unsigned short* logits, const long* labels,
                        ticket);
 }
 
-// the one launch of the SGD pass: clip_coef_dev picks the clipped
-// instantiations, nullptr the kernels (and argument lists) without it
+// the one launch of the SGD pass: lars_tab (with segs) picks the LARS
+// instantiations, clip_coef_dev the clipped ones (never both: the table holds
+// the coefficient already), nullptr the kernels (and argument lists) without
 static void sgd_step_launch(float* master, float* grad, unsigned short* shadow,
                             int has_shadow, long n, float lr_scale,
                             float dc_keep, uint64_t seed, uint64_t offset,
                             const float* lr_scale_dev, const long* offset_dev,
                             float* momentum, float mu, int zero_grad,
                             float* ema, float ema_decay,
-                            const float* clip_coef_dev, hipStream_t s) {
+                            const float* clip_coef_dev, const float* lars_tab,
+                            const GradNormSegs* segs, hipStream_t s) {
   long groups = (n + 3) / 4;
   int blocks = (int)min((long)2048, (groups + 255) / 256);
   if (blocks < 1) blocks = 1;
-  if (clip_coef_dev && ema)
+  if (lars_tab && ema)
+    hipLaunchKernelGGL(sgd_step_kernel_lars_ema, dim3(blocks), dim3(256), 0, s,
+                       master, grad, shadow, has_shadow, n, lr_scale, dc_keep,
+                       seed, offset, lr_scale_dev, offset_dev, momentum, mu,
+                       zero_grad, ema, ema_decay, lars_tab, *segs);
+  else if (lars_tab)
+    hipLaunchKernelGGL(sgd_step_kernel_lars, dim3(blocks), dim3(256), 0, s,
+                       master, grad, shadow, has_shadow, n, lr_scale, dc_keep,
+                       seed, offset, lr_scale_dev, offset_dev, momentum, mu,
+                       zero_grad, lars_tab, *segs);
+  else if (clip_coef_dev && ema)
     hipLaunchKernelGGL(sgd_step_kernel_clip_ema, dim3(blocks), dim3(256), 0, s,
                        master, grad, shadow, has_shadow, n, lr_scale, dc_keep,
                        seed, offset, lr_scale_dev, offset_dev, momentum, mu,
@@ -642,10 +741,11 @@ void launch_sgd_step(float* master, float* grad, unsigned short* shadow,
                      int has_shadow, long n, float lr_scale, float dc_keep,
                      uint64_t seed, uint64_t offset, float* momentum, float mu,
                      float* ema, float ema_decay, const float* clip_coef_dev,
+                     const float* lars_tab, const GradNormSegs* segs,
                      hipStream_t s) {
   sgd_step_launch(master, grad, shadow, has_shadow, n, lr_scale, dc_keep, seed,
                   offset, nullptr, nullptr, momentum, mu, 0, ema, ema_decay,
-                  clip_coef_dev, s);
+                  clip_coef_dev, lars_tab, segs, s);
 }
 
 void launch_sgd_step_dev(float* master, float* grad,
@@ -654,10 +754,11 @@ void launch_sgd_step_dev(float* master, float* grad,
                          uint64_t seed, const long* offset_dev,
                          float* momentum, float mu, int zero_grad,
                          float* ema, float ema_decay,
-                         const float* clip_coef_dev, hipStream_t s) {
+                         const float* clip_coef_dev, const float* lars_tab,
+                         const GradNormSegs* segs, hipStream_t s) {
   sgd_step_launch(master, grad, shadow, has_shadow, n, 0.f, dc_keep, seed, 0,
                   lr_scale_dev, offset_dev, momentum, mu, zero_grad, ema,
-                  ema_decay, clip_coef_dev, s);
+                  ema_decay, clip_coef_dev, lars_tab, segs, s);
 }
 
 // ---------------------------------------------------------------------------

@@ -102,6 +102,11 @@ class GraphedStep:
         clip0 = None
         if self._clip_stats is not None:
             clip0 = (self._clip_stats.clone(), t.clipped_steps.clone())
+        # --lars_eta: the warmup writes the trust-ratio tables too
+        self._lars_tab = getattr(t, "lars_tab", None)
+        lars0 = None
+        if self._lars_tab is not None:
+            lars0 = (self._lars_tab.clone(), t.lars_stats.clone())
         t.model.set_step_dev(self.step_dev)
 
         if self.split and self._fused is not None:
@@ -227,6 +232,9 @@ class GraphedStep:
                 if clip0 is not None:
                     self._clip_stats.copy_(clip0[0])
                     t.clipped_steps.copy_(clip0[1])
+                if lars0 is not None:
+                    self._lars_tab.copy_(lars0[0])
+                    t.lars_stats.copy_(lars0[1])
                 t.fp.sync_shadow()
                 t.model.set_step(t.step)
             except Exception:
@@ -245,6 +253,9 @@ class GraphedStep:
         if clip0 is not None:
             self._clip_stats.copy_(clip0[0])
             t.clipped_steps.copy_(clip0[1])
+        if lars0 is not None:
+            self._lars_tab.copy_(lars0[0])
+            t.lars_stats.copy_(lars0[1])
         t.fp.sync_shadow()
         self._prime(t.step)
         torch.cuda.synchronize()
@@ -294,7 +305,22 @@ class GraphedStep:
         t = self.t
         fp = t.fp
         clip_coef = None
-        if self._clip_stats is not None:
+        lars = {}
+        if self._lars_tab is not None:
+            # trust ratios (and, with --clip_grad_norm, the clip statistics)
+            # of the aggregated bucket in one launch, device-resident; its
+            # first call (warmup) runs outside capture and allocates the
+            # kernel's workspace
+            clipping = self._clip_stats is not None
+            self._ext.lars_norm(
+                fp.flat_master, fp.flat_grad, fp.offsets, fp.numels,
+                t.lars_adapt, self.inv_contrib, t.lars_eta, t.weight_decay,
+                t.clip if clipping else 0.0, self._lars_tab, t.lars_stats,
+                clip_stats=self._clip_stats,
+                clipped_steps=t.clipped_steps if clipping else None)
+            lars = dict(lars_tab=self._lars_tab, offsets=fp.offsets,
+                        numels=fp.numels)
+        elif self._clip_stats is not None:
             # norms + clip coefficient of the aggregated bucket, on the
             # device; every argument is device-resident or a capture
             # constant.  Its first call (warmup) runs outside capture and
@@ -315,7 +341,7 @@ class GraphedStep:
                                mu=t.flags.momentum, zero_grad=True,
                                ema=getattr(t, "flat_ema", None),
                                ema_decay=getattr(t, "ema_decay", 0.0),
-                               clip_coef=clip_coef)
+                               clip_coef=clip_coef, **lars)
         if fp._t_pairs:
             # transposes + step/LR advance in ONE dispatch
             self._ext.transpose_bf16_batch_adv(

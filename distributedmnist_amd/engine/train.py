@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import datetime
 import logging
+import math
 import os
 import time
 
@@ -234,6 +235,41 @@ class Trainer:
             self.clip_stats[1] = 1.0
             self.clipped_steps = torch.zeros(1, dtype=torch.int64,
                                              device=self.device)
+        # --lars_eta ETA > 0: LARS.  lars_norm reduces the master and the
+        # aggregated bucket to one trust ratio per tensor on the device and
+        # leaves (a_t, d_t) per tensor in lars_tab, which the SGD pass reads
+        # there: g = a_t*g, mask, g += d_t*w, momentum.  Tensors with
+        # dim() > 1 are adaptive and decayed (--weight_decay); biases keep
+        # ratio 1 and no decay.  With --clip_grad_norm the same launch also
+        # writes clip_stats (no grad_norm launch) and a_t carries the clip
+        # coefficient.  Every rank holds the same master and bucket: no
+        # collective.  With --drop_connect_post the ratio is that of the
+        # UNMASKED gradient.  Nothing of this is checkpointed.
+        self.lars_eta = float(getattr(flags, "lars_eta", 0.0) or 0.0)
+        self.weight_decay = float(getattr(flags, "weight_decay", 0.0) or 0.0)
+        if not 0.0 <= self.lars_eta < math.inf:
+            raise ValueError("--lars_eta must be 0 (off) or finite and > 0, "
+                             f"got {self.lars_eta}")
+        if not 0.0 <= self.weight_decay < math.inf:
+            raise ValueError("--weight_decay must be finite and >= 0, got "
+                             f"{self.weight_decay}")
+        if self.weight_decay > 0 and not self.lars_eta > 0:
+            raise ValueError("--weight_decay needs --lars_eta > 0")
+        self.lars_tab = self.lars_stats = None
+        self.lars_adapt = 0
+        if self.lars_eta > 0:
+            if len(self.fp.names) > 16:
+                raise ValueError("--lars_eta supports at most 16 parameter "
+                                 "tensors")
+            for i, p in enumerate(self.fp.params):
+                if p.dim() > 1:
+                    self.lars_adapt |= 1 << i
+            # 16 (a_t, d_t) pairs: (1, 0) until the first update
+            self.lars_tab = torch.tensor([1.0, 0.0] * 16, dtype=torch.float32,
+                                         device=self.device)
+            self.lars_stats = torch.zeros(3 * len(self.fp.names),
+                                          dtype=torch.float32,
+                                          device=self.device)
 
     # ------------------------------------------------------------------
     def to_device(self, images, labels):
@@ -472,7 +508,19 @@ class Trainer:
         lr = lr_at(lr_step, flags, self._num_examples,
                    max(1, self.engine.K))
         clip_coef = None
-        if self.clip_stats is not None:
+        lars = {}
+        if self.lars_tab is not None:
+            # one launch: trust ratios, and the clip statistics with them
+            Fx.lars_norm(self.fp.flat_master, grad, self.fp.offsets,
+                         self.fp.numels, self.lars_adapt,
+                         1.0 / max(1, contributors), self.lars_eta,
+                         self.weight_decay, self.clip,
+                         lars_tab=self.lars_tab, lars_stats=self.lars_stats,
+                         clip_stats=self.clip_stats,
+                         clipped_steps=self.clipped_steps)
+            lars = dict(lars_tab=self.lars_tab, offsets=self.fp.offsets,
+                        numels=self.fp.numels)
+        elif self.clip_stats is not None:
             Fx.grad_norm(grad, self.fp.offsets, self.fp.numels,
                          1.0 / max(1, contributors), self.clip,
                          stats=self.clip_stats,
@@ -488,7 +536,7 @@ class Trainer:
                     shadow=self.fp.flat_shadow,
                     momentum=self.flat_momentum, mu=flags.momentum,
                     ema=self.flat_ema, ema_decay=self.ema_decay,
-                    clip_coef=clip_coef)
+                    clip_coef=clip_coef, **lars)
         self.fp.refresh_transposes()
         self.num_contributors = contributors
 
@@ -505,6 +553,17 @@ class Trainer:
         out = {name: s[2 + i] for i, name in enumerate(self.fp.names)}
         out["global"], out["clip_coef"] = s[0], s[1]
         return out
+
+    def trust_ratios(self):
+        """{tensor name: (w_norm, g_norm, ratio)} of the most recent update
+        under --lars_eta (g_norm: the averaged, clipped gradient's; ratio 1
+        for the tensors LARS leaves alone).  Reads the device: for tools and
+        tests, not for the step loop."""
+        if self.lars_stats is None:
+            raise RuntimeError("trust_ratios() needs --lars_eta > 0")
+        s = self.lars_stats.detach().cpu().tolist()
+        return {name: tuple(s[3 * i:3 * i + 3])
+                for i, name in enumerate(self.fp.names)}
 
     # -- in-training evaluation (--eval_every_steps) ----------------------
     def attach_eval_dataset(self, ds):
@@ -650,6 +709,12 @@ class Trainer:
                                       self.step)
                     writer.add_scalar("Clip Coefficient", norms["clip_coef"],
                                       self.step)
+                if self.lars_stats is not None:
+                    ratios = self.trust_ratios()
+                    for i, name in enumerate(self.fp.names):
+                        if (self.lars_adapt >> i) & 1:
+                            writer.add_scalar(f"Trust Ratio/{name}",
+                                              ratios[name][2], self.step)
                 next_summary_time += flags.save_summaries_secs
             sv.maybe_save(self.step, self.checkpoint_payload)
         if self.mode == "interval":

@@ -12,6 +12,8 @@ ops/functional.py.
 
 from __future__ import annotations
 
+import math
+
 import torch
 import torch.nn.functional as F
 
@@ -192,8 +194,15 @@ def sgd_step(master, grad, lr: float, grad_scale: float = 1.0,
              drop_connect_keep: float | None = None,
              gen: torch.Generator | None = None, shadow=None,
              momentum=None, mu: float = 0.0, ema=None,
-             ema_decay: float = 0.0, offset: int = 0, clip_coef=None):
+             ema_decay: float = 0.0, offset: int = 0, clip_coef=None,
+             lars_tab=None, offsets=None, numels=None):
     """In-place w -= lr * grad_scale * (g or momentum-filtered g).
+
+    lars_tab (with offsets, numels; not with clip_coef): lars_norm()'s table.
+    Tensor t = [offsets[t], offsets[t] + numels[t]) does g = tab[2t]*g, then
+    the drop-connect mask, then the unmasked decay g += tab[2t + 1]*w (times
+    grad_scale: the table's decay entry is in units of the SUM over
+    contributors), then momentum.
 
     clip_coef: optional one-element fp32 tensor (grad_norm()'s stats[1:2]);
     the gradient is multiplied by it first, before the drop-connect mask and
@@ -213,11 +222,28 @@ def sgd_step(master, grad, lr: float, grad_scale: float = 1.0,
     """
     g = grad.float() * grad_scale
     if clip_coef is not None:
+        if lars_tab is not None:
+            raise ValueError("sgd_step: lars_tab and clip_coef are mutually "
+                             "exclusive")
         g = g * clip_coef.float().reshape(())
+    decay = None
+    if lars_tab is not None:
+        segs = torch.repeat_interleave(
+            torch.arange(len(offsets), device=g.device),
+            torch.tensor([int(m) for m in numels], device=g.device))
+        if segs.numel() != g.numel() or list(offsets) != [
+                sum(numels[:i]) for i in range(len(numels))]:
+            raise ValueError("sgd_step: the segments must tile [0, n) in "
+                             "order")
+        tab = lars_tab.float()
+        g = g * tab[2 * segs]
+        decay = (tab[2 * segs + 1] * grad_scale) * master
     if drop_connect_keep is not None:
         mask = (torch.rand(g.shape, device=g.device, dtype=torch.float32,
                            generator=gen) < drop_connect_keep).float()
         g = g * mask
+    if decay is not None:
+        g = g + decay
     if momentum is not None:
         momentum.mul_(mu).add_(g)
         g = momentum
@@ -275,6 +301,63 @@ def grad_norm(flat, offsets, numels, grad_scale: float, clip: float):
     out = [norm, coef] + [f32(float(grad_scale) * np.sqrt(v)) for v in sq]
     return torch.tensor([float(v) for v in out], dtype=torch.float32,
                         device=flat.device)
+
+
+def lars_norm(master, flat, offsets, numels, adapt_mask: int,
+              grad_scale: float, eta: float, wd: float, clip: float = 0.0):
+    """LARS trust ratios (You, Gitman, Ginsburg 2017) of the flat fp32
+    `master` and the flat fp32 gradient `flat` (the SUM over contributors,
+    grad_scale = s = 1 / contributors), the layout of csrc/lars.hip:
+
+      lars_tab[2t]     = a_t = ratio_t * coef
+      lars_tab[2t + 1] = d_t = ratio_t * wd / s     (0 if t is not adaptive)
+      lars_stats[3t:]  = (wn_t, gn_t, ratio_t)
+
+    wn_t = sqrt(sum w^2), gn_t = coef * (s * sqrt(sum g^2)), and for the
+    tensors whose bit is set in adapt_mask ratio_t = eta * wn_t / (gn_t + wd *
+    wn_t) when both norms are > 0; every other ratio is 1.  coef is
+    grad_norm()'s clip coefficient for clip > 0 and exactly 1 for clip = 0
+    (no clipping).  Sums in float64 from the fp32 values, everything after
+    them in fp32 in the order written here.  Returns (lars_tab [32], lars_stats
+    [3 * segments], clip_stats [2 + segments] or None)."""
+    import numpy as np
+    f32 = np.float32
+    if master.shape != flat.shape or master.dtype != torch.float32:
+        raise ValueError("lars_norm: master and flat are 1-D fp32 tensors of "
+                         "one length")
+    if not (eta > 0.0 and math.isfinite(eta)):
+        raise ValueError(f"lars_norm: eta must be finite and > 0, got {eta}")
+    if not (wd >= 0.0 and math.isfinite(wd)):
+        raise ValueError(f"lars_norm: wd must be finite and >= 0, got {wd}")
+    if not (grad_scale > 0.0 and math.isfinite(grad_scale)):
+        raise ValueError("lars_norm: grad_scale must be finite and > 0")
+    if not clip >= 0.0:
+        raise ValueError(f"lars_norm: clip must be 0 (off) or > 0, got {clip}")
+    ns = len(offsets)
+    if ns > 16 or not 0 <= adapt_mask < (1 << ns):
+        raise ValueError("lars_norm: at most 16 segments, one mask bit each")
+    # the table checks, the float64 segment sums and the coefficient
+    gstats = grad_norm(flat, offsets, numels, grad_scale,
+                       clip if clip > 0 else math.inf)
+    coef = f32(gstats[1].item()) if clip > 0 else f32(1)
+    w = master.detach().double()
+    s, eta32, wd32 = f32(grad_scale), f32(eta), f32(wd)
+    tab = np.zeros(32, dtype=np.float32)
+    tab[0::2] = 1.0
+    stats = np.zeros(3 * ns, dtype=np.float32)
+    for t, (o, m) in enumerate(zip(offsets, numels)):
+        wn = f32(np.sqrt(float((w[o:o + m] * w[o:o + m]).sum())))
+        gn = f32(coef * f32(gstats[2 + t].item()))
+        adaptive = bool((adapt_mask >> t) & 1)
+        ratio = f32(1)
+        if adaptive and wn > 0 and gn > 0:
+            ratio = f32(f32(eta32 * wn) / f32(gn + f32(wd32 * wn)))
+        tab[2 * t] = f32(ratio * coef)
+        tab[2 * t + 1] = f32(f32(ratio * wd32) / s) if adaptive else f32(0)
+        stats[3 * t:3 * t + 3] = (wn, gn, ratio)
+    dev = flat.device
+    return (torch.from_numpy(tab).to(dev), torch.from_numpy(stats).to(dev),
+            gstats if clip > 0 else None)
 
 
 def ema_weight(ema_decay: float, offset: int) -> float:

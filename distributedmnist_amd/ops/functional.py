@@ -330,12 +330,59 @@ def grad_norm(flat: torch.Tensor, offsets, numels, grad_scale: float,
     return stats
 
 
+def lars_norm(master: torch.Tensor, flat: torch.Tensor, offsets, numels,
+              adapt_mask: int, grad_scale: float, eta: float, wd: float,
+              clip: float = 0.0, lars_tab=None, lars_stats=None,
+              clip_stats=None, clipped_steps=None):
+    """LARS trust ratios of the flat fp32 `master` and the flat fp32 gradient
+    `flat` -> (`lars_tab` fp32 [32], `lars_stats` fp32 [3 * segments]), both
+    written in place when given (ops/cpu_ref.py::lars_norm).  clip > 0 also
+    fills `clip_stats` / counts in `clipped_steps` exactly as grad_norm()
+    does, so the caller needs no grad_norm() call.  On the GPU one
+    lars_norm_kernel launch: device-resident, hipGraph-capturable (after a
+    first call outside capture), no float atomics."""
+    offsets, numels = [int(o) for o in offsets], [int(m) for m in numels]
+    dev = flat.device
+    if lars_tab is None:
+        lars_tab = torch.zeros(32, dtype=torch.float32, device=dev)
+    if lars_stats is None:
+        lars_stats = torch.empty(3 * len(offsets), dtype=torch.float32,
+                                 device=dev)
+    if clip > 0 and clip_stats is None:
+        clip_stats = torch.empty(2 + len(offsets), dtype=torch.float32,
+                                 device=dev)
+    if flat.is_cuda:
+        if clip > 0 and clipped_steps is None:
+            clipped_steps = torch.zeros(1, dtype=torch.int64, device=dev)
+        _C.ext().lars_norm(master, flat, offsets, numels, int(adapt_mask),
+                           float(grad_scale), float(eta), float(wd),
+                           float(clip), lars_tab, lars_stats,
+                           clip_stats=clip_stats if clip > 0 else None,
+                           clipped_steps=clipped_steps if clip > 0 else None)
+    else:
+        tab, stats, cs = cpu_ref.lars_norm(master, flat, offsets, numels,
+                                           adapt_mask, grad_scale, eta, wd,
+                                           clip)
+        lars_tab.copy_(tab)
+        lars_stats.copy_(stats)
+        if cs is not None:
+            clip_stats.copy_(cs)
+            if clipped_steps is not None and float(cs[1]) < 1.0:
+                clipped_steps += 1
+    return lars_tab, lars_stats
+
+
 def sgd_step(master: torch.Tensor, grad: torch.Tensor, lr: float,
              grad_scale: float = 1.0, drop_connect_keep=None,
              seed: int = 0, offset: int = 0, shadow=None,
              momentum=None, mu: float = 0.0, ema=None,
-             ema_decay: float = 0.0, clip_coef=None):
+             ema_decay: float = 0.0, clip_coef=None, lars_tab=None,
+             offsets=None, numels=None):
     """Fused flat SGD apply: master -= lr*scale*(grad [* bernoulli(keep)]).
+
+    `lars_tab` (with `offsets`, `numels`; not with `clip_coef`): lars_norm()'s
+    table on master's device.  Tensor t does g = tab[2t]*g, the drop-connect
+    mask, the unmasked decay g += tab[2t + 1]*w, then momentum.
 
     `clip_coef` (optional one-element fp32 tensor on master's device,
     grad_norm()'s stats[1:2]) multiplies the gradient first, before the
@@ -350,6 +397,10 @@ def sgd_step(master: torch.Tensor, grad: torch.Tensor, lr: float,
     """
     if ema is not None and not 0.0 <= ema_decay < 1.0:
         raise ValueError(f"ema_decay must lie in [0, 1), got {ema_decay}")
+    lars = {}
+    if lars_tab is not None:
+        lars = dict(lars_tab=lars_tab, offsets=[int(o) for o in offsets],
+                    numels=[int(m) for m in numels])
     if master.is_cuda:
         _C.ext().sgd_step(master, grad,
                           shadow if shadow is not None else master,
@@ -357,7 +408,8 @@ def sgd_step(master: torch.Tensor, grad: torch.Tensor, lr: float,
                           -1.0 if drop_connect_keep is None else float(drop_connect_keep),
                           int(seed), int(offset),
                           momentum=momentum, mu=float(mu), ema=ema,
-                          ema_decay=float(ema_decay), clip_coef=clip_coef)
+                          ema_decay=float(ema_decay), clip_coef=clip_coef,
+                          **lars)
     else:
         gen = None
         if drop_connect_keep is not None:
@@ -367,4 +419,4 @@ def sgd_step(master: torch.Tensor, grad: torch.Tensor, lr: float,
                          drop_connect_keep, gen, shadow,
                          momentum=momentum, mu=mu, ema=ema,
                          ema_decay=ema_decay, offset=offset,
-                         clip_coef=clip_coef)
+                         clip_coef=clip_coef, **lars)

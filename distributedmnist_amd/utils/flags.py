@@ -38,6 +38,29 @@ def _clip(text: str) -> float:
     return v
 
 
+def _lars_eta(text: str) -> float:
+    """--lars_eta: 0 (off) or a finite trust coefficient > 0."""
+    try:
+        v = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a number: {text!r}")
+    if not 0.0 <= v < float("inf"):  # also refuses nan
+        raise argparse.ArgumentTypeError(
+            f"must be 0 (off) or finite and > 0, got {text}")
+    return v
+
+
+class _TrainParser(argparse.ArgumentParser):
+    """Checks that span two flags, reported as argument errors."""
+
+    def parse_known_args(self, args=None, namespace=None):
+        ns, rest = super().parse_known_args(args, namespace)
+        if ns.weight_decay > 0 and not ns.lars_eta > 0:
+            self.error("argument --weight_decay: needs --lars_eta > 0 (the "
+                       "decay is applied by the LARS update only)")
+        return ns, rest
+
+
 def _in_range(lo: float, hi: float):
     """argparse type: a float in [lo, hi]."""
     def parse(text: str) -> float:
@@ -53,7 +76,7 @@ def _in_range(lo: float, hi: float):
 
 
 def build_train_parser() -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser(description="MI355X-native distributed MNIST training")
+    p = _TrainParser(description="MI355X-native distributed MNIST training")
     # --- reference-compatible flags (distributed_train.py:36-99) ---
     p.add_argument("--worker_times_cdf_method", action="store_true",
                    help="collect per-worker compute-time CDFs (DP-2 mode)")
@@ -180,6 +203,19 @@ def build_train_parser() -> argparse.ArgumentParser:
                         "order (no host round trip, same bits on every "
                         "rank). inf never clips and only reports the norms; "
                         "0 = off")
+    p.add_argument("--lars_eta", type=_lars_eta, default=0.0, metavar="ETA",
+                   help="ETA > 0: layer-wise adaptive rate scaling (LARS, You "
+                        "et al. 2017). Every weight tensor's step is scaled "
+                        "by ETA * |w| / (|g| + WD * |w|), the norms reduced "
+                        "on the device in one launch in a fixed order (no "
+                        "host round trip, same bits on every rank); biases "
+                        "are left alone. With --clip_grad_norm the same "
+                        "launch also clips. 0 = off")
+    p.add_argument("--weight_decay", type=_in_range(0.0, float("inf")),
+                   default=0.0, metavar="WD",
+                   help="L2 weight decay of the LARS update (weight tensors "
+                        "only): g += WD * w inside the trust ratio and the "
+                        "step. Needs --lars_eta")
     p.add_argument("--deterministic", action="store_true",
                    help="bitwise-reproducible gradients on the GPU: the fused "
                         "LeNet step reduces every weight and bias gradient "
