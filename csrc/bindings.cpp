@@ -1351,6 +1351,176 @@ void lars_norm(torch::Tensor master, torch::Tensor grad,
                    lars_stats.data_ptr<float>(), cs, cnt, part, ticket, s);
 }
 
+// ---- Adam / AdamW and LAMB (adam.hip) --------------------------------------
+// What the three bindings share: the flat fp32 streams (16 B aligned, on one
+// device), the hyper-parameters and the optional device copies of lr_scale
+// and the offset (both or neither; given, the launch is graph-capturable).
+struct AdamCall {
+  AdamArgs a;
+  GradNormSegs segs;
+  long n;
+  float lr_scale;
+  const float* lr_scale_dev;
+  const long* offset_dev;
+};
+
+static AdamCall adam_call(const char* who, const torch::Tensor& master,
+                          std::initializer_list<const torch::Tensor*> streams,
+                          double lr, double scale, double beta1, double beta2,
+                          double eps, double wd,
+                          const std::vector<int64_t>& offsets,
+                          const std::vector<int64_t>& numels,
+                          int64_t adapt_mask, double dc_keep, int64_t seed,
+                          const c10::optional<torch::Tensor>& lr_scale_dev,
+                          const c10::optional<torch::Tensor>& offset_dev) {
+  CHECK_CUDA(master); CHECK_F32(master); CHECK_CONTIG(master);
+  const int64_t n = master.numel();
+  TORCH_CHECK(n >= 1, who, ": empty master");
+  for (const torch::Tensor* t : streams) {
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat &&
+                t->is_contiguous() && t->numel() == n &&
+                t->get_device() == master.get_device() &&
+                reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                who, ": grad and the moments are contiguous fp32 tensors of "
+                "master's length on its device, 16-byte aligned");
+  }
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(master.data_ptr()) % 16 == 0,
+              who, ": master must be 16-byte aligned");
+  TORCH_CHECK(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0,
+              who, ": beta1 and beta2 must lie in [0, 1)");
+  TORCH_CHECK(eps > 0.0 && std::isfinite(eps),
+              who, ": eps must be finite and > 0");
+  TORCH_CHECK(wd >= 0.0 && std::isfinite(wd),
+              who, ": wd must be finite and >= 0");
+  const double contrib = std::nearbyint(1.0 / scale);
+  TORCH_CHECK(scale > 0.0 && scale <= 1.0 &&
+              std::fabs(1.0 / scale - contrib) <= 1e-6 * contrib,
+              who, ": scale must be 1 / contributors");
+  AdamCall c{};
+  c.n = n;
+  c.segs = tiling_segs(who, offsets, numels, n);
+  TORCH_CHECK(adapt_mask >= 0 && adapt_mask < (int64_t(1) << c.segs.n),
+              who, ": adapt_mask has one bit per segment");
+  c.a = AdamArgs{beta1, beta2, eps, wd, (float)std::log(beta1),
+                 (float)std::log(beta2), (float)scale, (unsigned)adapt_mask,
+                 (float)dc_keep, (uint64_t)seed};
+  c.lr_scale = (float)(lr * scale);
+  const bool dev = lr_scale_dev.has_value() && lr_scale_dev->defined();
+  TORCH_CHECK(dev == (offset_dev.has_value() && offset_dev->defined()),
+              who, ": lr_scale_dev and offset_dev come together");
+  if (dev) {
+    TORCH_CHECK(lr_scale_dev->is_cuda() &&
+                lr_scale_dev->scalar_type() == at::kFloat &&
+                offset_dev->is_cuda() &&
+                offset_dev->scalar_type() == at::kLong &&
+                lr_scale_dev->numel() == 1 && offset_dev->numel() == 1,
+                who, ": lr_scale_dev is one fp32, offset_dev one int64, both "
+                "on the GPU");
+    c.lr_scale_dev = lr_scale_dev->data_ptr<float>();
+    c.offset_dev = offset_dev->data_ptr<long>();
+  }
+  return c;
+}
+
+static unsigned short* adam_shadow(const c10::optional<torch::Tensor>& shadow,
+                                   const torch::Tensor& master) {
+  if (!shadow.has_value() || !shadow->defined()) return nullptr;
+  CHECK_CUDA((*shadow)); CHECK_BF16((*shadow)); CHECK_CONTIG((*shadow));
+  TORCH_CHECK(shadow->numel() >= master.numel(),
+              "adam: shadow is shorter than master");
+  return reinterpret_cast<unsigned short*>(shadow->data_ptr());
+}
+
+void adam_step(torch::Tensor master, torch::Tensor grad, torch::Tensor am,
+               torch::Tensor av, double lr, double scale, double beta1,
+               double beta2, double eps, double wd,
+               std::vector<int64_t> offsets, std::vector<int64_t> numels,
+               int64_t adapt_mask, double dc_keep, int64_t seed,
+               int64_t offset, c10::optional<torch::Tensor> shadow,
+               c10::optional<torch::Tensor> ema, double ema_decay,
+               c10::optional<torch::Tensor> clip_coef,
+               c10::optional<torch::Tensor> lr_scale_dev,
+               c10::optional<torch::Tensor> offset_dev, bool zero_grad) {
+  AdamCall c = adam_call("adam_step", master, {&grad, &am, &av}, lr, scale,
+                         beta1, beta2, eps, wd, offsets, numels, adapt_mask,
+                         dc_keep, seed, lr_scale_dev, offset_dev);
+  launch_adam_step(master.data_ptr<float>(), grad.data_ptr<float>(),
+                   am.data_ptr<float>(), av.data_ptr<float>(),
+                   adam_shadow(shadow, master), c.n, c.a, c.segs, c.lr_scale,
+                   (uint64_t)offset, c.lr_scale_dev, c.offset_dev,
+                   zero_grad ? 1 : 0, ema_ptr(ema, master, ema_decay),
+                   (float)ema_decay, clip_coef_ptr(clip_coef, master),
+                   cur_stream());
+}
+
+void lamb_moments(torch::Tensor master, torch::Tensor grad, torch::Tensor am,
+                  torch::Tensor av, double scale, double beta1, double beta2,
+                  double eps, double wd, std::vector<int64_t> offsets,
+                  std::vector<int64_t> numels, int64_t adapt_mask,
+                  double dc_keep, int64_t seed, int64_t offset,
+                  torch::Tensor lamb_tab, torch::Tensor lamb_stats,
+                  c10::optional<torch::Tensor> clip_coef,
+                  c10::optional<torch::Tensor> offset_dev) {
+  AdamCall c = adam_call("lamb_moments", master, {&grad, &am, &av}, 0.0, scale,
+                         beta1, beta2, eps, wd, offsets, numels, adapt_mask,
+                         dc_keep, seed, c10::nullopt, c10::nullopt);
+  const long* off_dev = nullptr;
+  if (offset_dev.has_value() && offset_dev->defined()) {
+    TORCH_CHECK(offset_dev->is_cuda() && offset_dev->numel() == 1 &&
+                offset_dev->scalar_type() == at::kLong,
+                "lamb_moments: offset_dev is one int64 on the GPU");
+    off_dev = offset_dev->data_ptr<long>();
+  }
+  CHECK_CUDA(lamb_tab); CHECK_F32(lamb_tab); CHECK_CONTIG(lamb_tab);
+  CHECK_CUDA(lamb_stats); CHECK_F32(lamb_stats); CHECK_CONTIG(lamb_stats);
+  TORCH_CHECK(lamb_tab.numel() == GRAD_NORM_MAX_SEGS &&
+              lamb_stats.numel() == 3 * c.segs.n &&
+              lamb_tab.get_device() == master.get_device() &&
+              lamb_stats.get_device() == master.get_device(),
+              "lamb_moments: lamb_tab holds ", GRAD_NORM_MAX_SEGS,
+              " values, lamb_stats 3 per segment, on master's device");
+  auto s = cur_stream();
+  static auto* ws = new WorkspaceSlots(64);
+  const int64_t half = GRAD_NORM_MAX_SEGS * GRAD_NORM_MAX_BLOCKS;
+  float* part = device_workspace(
+      *ws, master, 2 * half + 1, at::kFloat, s, "lamb_moments",
+      "lamb_moments: first call on a device allocates its workspace and must "
+      "run outside graph capture").data_ptr<float>();
+  unsigned* ticket = reinterpret_cast<unsigned*>(part + 2 * half);
+  launch_lamb_moments(master.data_ptr<float>(), grad.data_ptr<float>(),
+                      am.data_ptr<float>(), av.data_ptr<float>(), c.n, c.a,
+                      c.segs, (uint64_t)offset, off_dev,
+                      clip_coef_ptr(clip_coef, master),
+                      lamb_tab.data_ptr<float>(),
+                      lamb_stats.data_ptr<float>(), part, ticket, s);
+}
+
+void lamb_apply(torch::Tensor master, torch::Tensor grad, torch::Tensor am,
+                torch::Tensor av, double lr, double scale, double beta1,
+                double beta2, double eps, double wd,
+                std::vector<int64_t> offsets, std::vector<int64_t> numels,
+                int64_t adapt_mask, int64_t offset, torch::Tensor lamb_tab,
+                c10::optional<torch::Tensor> shadow,
+                c10::optional<torch::Tensor> ema, double ema_decay,
+                c10::optional<torch::Tensor> lr_scale_dev,
+                c10::optional<torch::Tensor> offset_dev, bool zero_grad) {
+  AdamCall c = adam_call("lamb_apply", master, {&grad, &am, &av}, lr, scale,
+                         beta1, beta2, eps, wd, offsets, numels, adapt_mask,
+                         -1.0, 0, lr_scale_dev, offset_dev);
+  CHECK_CUDA(lamb_tab); CHECK_F32(lamb_tab); CHECK_CONTIG(lamb_tab);
+  TORCH_CHECK(lamb_tab.numel() == GRAD_NORM_MAX_SEGS &&
+              lamb_tab.get_device() == master.get_device(),
+              "lamb_apply: lamb_tab holds ", GRAD_NORM_MAX_SEGS,
+              " values on master's device");
+  launch_lamb_apply(master.data_ptr<float>(), grad.data_ptr<float>(),
+                    am.data_ptr<float>(), av.data_ptr<float>(),
+                    adam_shadow(shadow, master), c.n, c.a, c.segs, c.lr_scale,
+                    (uint64_t)offset, c.lr_scale_dev, c.offset_dev,
+                    zero_grad ? 1 : 0, ema_ptr(ema, master, ema_decay),
+                    (float)ema_decay, lamb_tab.data_ptr<float>(),
+                    cur_stream());
+}
+
 void ema_publish(torch::Tensor ema, torch::Tensor shadow,
                  std::vector<int64_t> offsets, std::vector<int64_t> rows,
                  std::vector<int64_t> cols, std::vector<torch::Tensor> dsts) {
@@ -1779,6 +1949,47 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           lars_norm_plan((long)n, &blocks, &chain);
           return std::make_tuple(blocks, chain);
         }, "(blocks, chain) of lars_norm on n elements: grad_norm's grid; "
+        "each of the two sums is a chain of that length");
+  m.def("adam_step", &adam_step,
+        "fused flat Adam / AdamW apply: moments, bias correction, decoupled "
+        "decay on the tensors of adapt_mask, the weight write, the moving "
+        "average, the bf16 shadow; lr_scale_dev + offset_dev make it "
+        "hipGraph-capturable, zero_grad clears the bucket in the same pass",
+        py::arg("master"), py::arg("grad"), py::arg("m"), py::arg("v"),
+        py::arg("lr"), py::arg("scale"), py::arg("beta1"), py::arg("beta2"),
+        py::arg("eps"), py::arg("wd"), py::arg("offsets"), py::arg("numels"),
+        py::arg("adapt_mask"), py::arg("dc_keep"), py::arg("seed"),
+        py::arg("offset"), py::arg("shadow") = c10::nullopt,
+        py::arg("ema") = c10::nullopt, py::arg("ema_decay") = 0.0,
+        py::arg("clip_coef") = c10::nullopt,
+        py::arg("lr_scale_dev") = c10::nullopt,
+        py::arg("offset_dev") = c10::nullopt, py::arg("zero_grad") = false);
+  m.def("lamb_moments", &lamb_moments,
+        "LAMB pass 1: m, v in place; lamb_tab[t] = r_t, lamb_stats[3t..] = "
+        "(|w_t|, |u_t|, r_t); one launch, no float atomics",
+        py::arg("master"), py::arg("grad"), py::arg("m"), py::arg("v"),
+        py::arg("scale"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"),
+        py::arg("wd"), py::arg("offsets"), py::arg("numels"),
+        py::arg("adapt_mask"), py::arg("dc_keep"), py::arg("seed"),
+        py::arg("offset"), py::arg("lamb_tab"), py::arg("lamb_stats"),
+        py::arg("clip_coef") = c10::nullopt,
+        py::arg("offset_dev") = c10::nullopt);
+  m.def("lamb_apply", &lamb_apply,
+        "LAMB pass 2: w -= (lr * r_t) * u_t from pass 1's m, v and table; the "
+        "moving average, the bf16 shadow, the cleared bucket",
+        py::arg("master"), py::arg("grad"), py::arg("m"), py::arg("v"),
+        py::arg("lr"), py::arg("scale"), py::arg("beta1"), py::arg("beta2"),
+        py::arg("eps"), py::arg("wd"), py::arg("offsets"), py::arg("numels"),
+        py::arg("adapt_mask"), py::arg("offset"), py::arg("lamb_tab"),
+        py::arg("shadow") = c10::nullopt, py::arg("ema") = c10::nullopt,
+        py::arg("ema_decay") = 0.0, py::arg("lr_scale_dev") = c10::nullopt,
+        py::arg("offset_dev") = c10::nullopt, py::arg("zero_grad") = false);
+  m.def("lamb_norm_plan", [](int64_t n) {
+          TORCH_CHECK(n >= 1, "lamb_norm_plan: n must be >= 1");
+          int blocks, chain;
+          lamb_norm_plan((long)n, &blocks, &chain);
+          return std::make_tuple(blocks, chain);
+        }, "(blocks, chain) of lamb_moments on n elements: grad_norm's grid; "
         "each of the two sums is a chain of that length");
   m.def("ema_publish", &ema_publish,
         "flat fp32 parameters -> flat bf16 shadow + transposed bf16 copies "

@@ -169,6 +169,48 @@ void launch_lars_norm(const float* master, const float* grad, long n,
                       float* lars_stats, float* clip_stats,
                       long* clipped_steps, float* part, unsigned* ticket,
                       hipStream_t);
+// adam.hip — Adam / AdamW and LAMB on the flat fp32 bucket (--optimizer).
+// am / av: the fp32 moments, master's layout, 16 B aligned like master and
+// grad.  lnb1 / lnb2: ln(beta) rounded once from double; grad_scale = 1 /
+// contributors (the kernels use lr = lr_scale * contributors); adapt: bit t
+// set = tensor t of segs is decayed by wd (and, under LAMB, trust-scaled);
+// dc_keep > 0: sgd_step's drop-connect mask.  offset_dev / lr_scale_dev !=
+// nullptr: read on the device instead of offset / lr_scale (graph capture).
+// shadow, ema, clip_coef_dev: optional, as in launch_sgd_step.
+struct AdamArgs {
+  double beta1, beta2, eps, wd;
+  float lnb1, lnb2, grad_scale;
+  unsigned adapt;
+  float dc_keep;
+  uint64_t seed;
+};
+void launch_adam_step(float* master, float* grad, float* am, float* av,
+                      unsigned short* shadow, long n, const AdamArgs& a,
+                      const GradNormSegs& segs, float lr_scale,
+                      uint64_t offset, const float* lr_scale_dev,
+                      const long* offset_dev, int zero_grad, float* ema,
+                      float ema_decay, const float* clip_coef_dev,
+                      hipStream_t);
+// LAMB pass 1: am, av updated in place; STORED: lamb_tab[t] = r_t (one float
+// per segment, GRAD_NORM_MAX_SEGS in all), lamb_stats[3t ..] = (||w_t||,
+// ||u_t||, r_t), r_t = ||w_t|| / ||u_t|| for adaptive tensors with both norms
+// > 0, else 1.  part/ticket: a workspace of its own, sized like lars_norm's.
+// Pass 2 reads lamb_tab on the device and writes master, the average, the
+// shadow and (zero_grad) the cleared gradient.
+void lamb_norm_plan(long n, int* blocks, int* chain);
+void launch_lamb_moments(const float* master, const float* grad, float* am,
+                         float* av, long n, const AdamArgs& a,
+                         const GradNormSegs& segs, uint64_t offset,
+                         const long* offset_dev, const float* clip_coef_dev,
+                         float* lamb_tab, float* lamb_stats, float* part,
+                         unsigned* ticket, hipStream_t);
+void launch_lamb_apply(float* master, float* grad, const float* am,
+                       const float* av, unsigned short* shadow, long n,
+                       const AdamArgs& a, const GradNormSegs& segs,
+                       float lr_scale, uint64_t offset,
+                       const float* lr_scale_dev, const long* offset_dev,
+                       int zero_grad, float* ema, float ema_decay,
+                       const float* lamb_tab, hipStream_t);
 // ema != nullptr (both launchers): the same pass also moves the fp32 moving
 // average towards the new master, e -= (1 - d_k)*(e - w) with
 // d_k = min(ema_decay, (1 + k)/(10 + k)), k = offset + 1 (a second

@@ -107,6 +107,13 @@ class GraphedStep:
         lars0 = None
         if self._lars_tab is not None:
             lars0 = (self._lars_tab.clone(), t.lars_stats.clone())
+        # --optimizer adam|lamb: the warmup moves the moments (and writes
+        # LAMB's table) too; (buffer, snapshot) pairs to roll back
+        lamb = getattr(t, "lamb_tab", None) is not None
+        adam0 = [(b, b.clone()) for b in (
+            getattr(t, "flat_adam_m", None), getattr(t, "flat_adam_v", None),
+            getattr(t, "lamb_tab", None), t.lars_stats if lamb else None)
+            if b is not None]
         t.model.set_step_dev(self.step_dev)
 
         if self.split and self._fused is not None:
@@ -235,6 +242,8 @@ class GraphedStep:
                 if lars0 is not None:
                     self._lars_tab.copy_(lars0[0])
                     t.lars_stats.copy_(lars0[1])
+                for buf, snap in adam0:
+                    buf.copy_(snap)
                 t.fp.sync_shadow()
                 t.model.set_step(t.step)
             except Exception:
@@ -256,6 +265,8 @@ class GraphedStep:
         if lars0 is not None:
             self._lars_tab.copy_(lars0[0])
             t.lars_stats.copy_(lars0[1])
+        for buf, snap in adam0:
+            buf.copy_(snap)
         t.fp.sync_shadow()
         self._prime(t.step)
         torch.cuda.synchronize()
@@ -331,17 +342,24 @@ class GraphedStep:
             clip_coef = self._clip_stats[1:2]
         # zero_grad=True: the bucket is cleared in the same pass that
         # consumes it — no per-step fill kernel in the replayed graph
-        self._ext.sgd_step_dev(fp.flat_master, fp.flat_grad,
-                               fp.flat_shadow if fp.flat_shadow is not None
-                               else fp.flat_master,
-                               fp.flat_shadow is not None,
-                               self.lr_scale_dev, self.dc_keep,
-                               t.flags.seed, self.step_dev,
-                               momentum=t.flat_momentum,
-                               mu=t.flags.momentum, zero_grad=True,
-                               ema=getattr(t, "flat_ema", None),
-                               ema_decay=getattr(t, "ema_decay", 0.0),
-                               clip_coef=clip_coef, **lars)
+        if getattr(t, "optimizer", "sgd") != "sgd":
+            # adam_step_kernel, or LAMB's two launches (the first call of
+            # lamb_moments, in the warmup, allocates its workspace); lr and
+            # the update count are read on the device
+            t.adam_update(fp.flat_grad, 0.0, self.inv_contrib,
+                          self.dc_keep if self.dc_keep > 0 else None, 0,
+                          clip_coef, lr_scale_dev=self.lr_scale_dev,
+                          offset_dev=self.step_dev, zero_grad=True)
+        else:
+            self._ext.sgd_step_dev(
+                fp.flat_master, fp.flat_grad,
+                fp.flat_shadow if fp.flat_shadow is not None
+                else fp.flat_master, fp.flat_shadow is not None,
+                self.lr_scale_dev, self.dc_keep, t.flags.seed, self.step_dev,
+                momentum=t.flat_momentum, mu=t.flags.momentum, zero_grad=True,
+                ema=getattr(t, "flat_ema", None),
+                ema_decay=getattr(t, "ema_decay", 0.0),
+                clip_coef=clip_coef, **lars)
         if fp._t_pairs:
             # transposes + step/LR advance in ONE dispatch
             self._ext.transpose_bf16_batch_adv(

@@ -253,8 +253,40 @@ class Trainer:
         if not 0.0 <= self.weight_decay < math.inf:
             raise ValueError("--weight_decay must be finite and >= 0, got "
                              f"{self.weight_decay}")
-        if self.weight_decay > 0 and not self.lars_eta > 0:
-            raise ValueError("--weight_decay needs --lars_eta > 0")
+        # --optimizer adam|lamb: Adam / AdamW and LAMB on the flat bucket
+        # (ops.functional.adam_step / lamb_step).  Two fp32 moment buffers in
+        # the master's layout, checkpointed; decay and LAMB's trust ratio on
+        # the tensors with dim() > 1 (the set LARS adapts), plain Adam on the
+        # biases.  Every rank holds the same master and bucket: no collective.
+        self.optimizer = getattr(flags, "optimizer", "sgd") or "sgd"
+        if self.optimizer not in ("sgd", "adam", "lamb"):
+            raise ValueError(f"--optimizer must be sgd, adam or lamb, got "
+                             f"{self.optimizer}")
+        if self.optimizer != "sgd" and (flags.momentum > 0
+                                        or self.lars_eta > 0):
+            raise ValueError(f"--optimizer {self.optimizer} cannot be "
+                             "combined with --momentum or --lars_eta")
+        self.flat_adam_m = self.flat_adam_v = None
+        self.lamb_tab = None
+        if self.optimizer != "sgd":
+            if len(self.fp.names) > 16:
+                raise ValueError(f"--optimizer {self.optimizer} supports at "
+                                 "most 16 parameter tensors")
+            # the parser has filled the defaults; 0 is a legal beta
+            self.adam = dict(
+                beta1=float(flags.adam_beta1), beta2=float(flags.adam_beta2),
+                eps=float(flags.adam_eps),
+                wd=self.weight_decay, offsets=self.fp.offsets,
+                numels=self.fp.numels, adapt_mask=0)
+            for i, p in enumerate(self.fp.params):
+                if p.dim() > 1:
+                    self.adam["adapt_mask"] |= 1 << i
+            self.flat_adam_m = torch.zeros_like(self.fp.flat_master)
+            self.flat_adam_v = torch.zeros_like(self.fp.flat_master)
+        if (self.weight_decay > 0 and not self.lars_eta > 0
+                and self.optimizer == "sgd"):
+            raise ValueError("--weight_decay needs --lars_eta > 0 or "
+                             "--optimizer adam|lamb")
         self.lars_tab = self.lars_stats = None
         self.lars_adapt = 0
         if self.lars_eta > 0:
@@ -267,6 +299,16 @@ class Trainer:
             # 16 (a_t, d_t) pairs: (1, 0) until the first update
             self.lars_tab = torch.tensor([1.0, 0.0] * 16, dtype=torch.float32,
                                          device=self.device)
+            self.lars_stats = torch.zeros(3 * len(self.fp.names),
+                                          dtype=torch.float32,
+                                          device=self.device)
+        if self.optimizer == "lamb":
+            # r_t per tensor (1 until the first update) and (w_norm, u_norm,
+            # ratio) per tensor: trust_ratios() and the summaries read
+            # lars_stats / lars_adapt under either optimizer
+            self.lars_adapt = self.adam["adapt_mask"]
+            self.lamb_tab = torch.ones(16, dtype=torch.float32,
+                                       device=self.device)
             self.lars_stats = torch.zeros(3 * len(self.fp.names),
                                           dtype=torch.float32,
                                           device=self.device)
@@ -527,18 +569,37 @@ class Trainer:
                          clipped_steps=self.clipped_steps)
             clip_coef = self.clip_stats[1:2]
         self.clip_updates += 1
-        Fx.sgd_step(self.fp.flat_master, grad, lr,
-                    grad_scale=1.0 / max(1, contributors),
-                    drop_connect_keep=(flags.drop_connect_probability
-                                       if (flags.drop_connect
-                                           and not self._dc_pre) else None),
-                    seed=flags.seed, offset=lr_step,
-                    shadow=self.fp.flat_shadow,
-                    momentum=self.flat_momentum, mu=flags.momentum,
-                    ema=self.flat_ema, ema_decay=self.ema_decay,
-                    clip_coef=clip_coef, **lars)
+        dc_keep = (flags.drop_connect_probability
+                   if (flags.drop_connect and not self._dc_pre) else None)
+        if self.optimizer != "sgd":
+            self.adam_update(grad, lr, 1.0 / max(1, contributors), dc_keep,
+                             lr_step, clip_coef)
+        else:
+            Fx.sgd_step(self.fp.flat_master, grad, lr,
+                        grad_scale=1.0 / max(1, contributors),
+                        drop_connect_keep=dc_keep,
+                        seed=flags.seed, offset=lr_step,
+                        shadow=self.fp.flat_shadow,
+                        momentum=self.flat_momentum, mu=flags.momentum,
+                        ema=self.flat_ema, ema_decay=self.ema_decay,
+                        clip_coef=clip_coef, **lars)
         self.fp.refresh_transposes()
         self.num_contributors = contributors
+
+    def adam_update(self, grad, lr, grad_scale, dc_keep, offset, clip_coef,
+                    **dev):
+        """The --optimizer adam|lamb update of one aggregated gradient.
+        dev: lr_scale_dev, offset_dev, zero_grad of the graph-captured tail
+        (lr and offset are then read on the device)."""
+        kw = dict(self.adam, drop_connect_keep=dc_keep, seed=self.flags.seed,
+                  offset=offset, shadow=self.fp.flat_shadow,
+                  ema=self.flat_ema, ema_decay=self.ema_decay,
+                  clip_coef=clip_coef, **dev)
+        if self.optimizer == "lamb":
+            kw.update(lamb_tab=self.lamb_tab, lamb_stats=self.lars_stats)
+        step = Fx.adam_step if self.optimizer == "adam" else Fx.lamb_step
+        step(self.fp.flat_master, grad, self.flat_adam_m, self.flat_adam_v,
+             lr, grad_scale, **kw)
 
     def grad_norms(self):
         """Norms of the most recent aggregated (averaged) gradient under
@@ -557,10 +618,12 @@ class Trainer:
     def trust_ratios(self):
         """{tensor name: (w_norm, g_norm, ratio)} of the most recent update
         under --lars_eta (g_norm: the averaged, clipped gradient's; ratio 1
-        for the tensors LARS leaves alone).  Reads the device: for tools and
-        tests, not for the step loop."""
+        for the tensors LARS leaves alone); under --optimizer lamb {tensor
+        name: (w_norm, u_norm, ratio)} with u the decayed Adam update.  Reads
+        the device: for tools and tests, not for the step loop."""
         if self.lars_stats is None:
-            raise RuntimeError("trust_ratios() needs --lars_eta > 0")
+            raise RuntimeError("trust_ratios() needs --lars_eta > 0 or "
+                               "--optimizer lamb")
         s = self.lars_stats.detach().cpu().tolist()
         return {name: tuple(s[3 * i:3 * i + 3])
                 for i, name in enumerate(self.fp.names)}
@@ -618,6 +681,20 @@ class Trainer:
                     and payload.get("flat_momentum") is not None):
                 self.flat_momentum.copy_(
                     payload["flat_momentum"].to(self.device))
+            if self.flat_adam_m is not None:
+                if (payload.get("flat_adam_m") is not None
+                        and payload.get("flat_adam_v") is not None):
+                    self.flat_adam_m.copy_(
+                        payload["flat_adam_m"].to(self.device))
+                    self.flat_adam_v.copy_(
+                        payload["flat_adam_v"].to(self.device))
+                else:
+                    log.warning(
+                        "checkpoint at step %d carries no Adam moments (it "
+                        "was written without --optimizer adam|lamb): "
+                        "starting them at zero", step0)
+                    self.flat_adam_m.zero_()
+                    self.flat_adam_v.zero_()
             if self.flat_ema is not None:
                 if payload.get("flat_ema") is not None:
                     self.flat_ema.copy_(payload["flat_ema"].to(self.device))
@@ -745,6 +822,10 @@ class Trainer:
                               if self.flat_momentum is not None else None),
             "flat_ema": (self.flat_ema.detach().cpu().clone()
                          if self.flat_ema is not None else None),
+            "flat_adam_m": (self.flat_adam_m.detach().cpu().clone()
+                            if self.flat_adam_m is not None else None),
+            "flat_adam_v": (self.flat_adam_v.detach().cpu().clone()
+                            if self.flat_adam_v is not None else None),
             "model_state": {k: v.cpu() for k, v in
                             self.fp.state_dict_params().items()},
             "model": self.flags.model,

@@ -360,6 +360,173 @@ def lars_norm(master, flat, offsets, numels, adapt_mask: int,
             gstats if clip > 0 else None)
 
 
+# ---------------------------------------------------------------------------
+# Adam / AdamW and LAMB (--optimizer; csrc/adam.hip).  Every fp32 operation
+# below is one torch op or one numpy.float32 op, in the kernels' order.
+# ---------------------------------------------------------------------------
+
+def adam_constants(lr: float, grad_scale: float, beta1: float, beta2: float,
+                   offset: int):
+    """(lr, c1, c2) of update k = offset + 1 as the kernels form them, in
+    numpy.float32: lr = fl(lr * s) * contributors, c = 1 - beta^k as the
+    correctly rounded -expm1 of the fp32 product k * ln(beta), ln(beta)
+    rounded once from double."""
+    import numpy as np
+    f32 = np.float32
+    contrib = f32(round(1.0 / grad_scale))
+    k = f32(int(offset) + 1)
+    with np.errstate(invalid="ignore"):
+        c = [f32(-np.expm1(np.float64(
+            k * f32(math.log(b) if b > 0 else -math.inf))))
+            for b in (beta1, beta2)]
+    return f32(lr * grad_scale) * contrib, c[0], c[1]
+
+
+def _adam_check(master, beta1, beta2, eps, wd, grad_scale):
+    if master.dtype != torch.float32 or master.dim() != 1:
+        raise ValueError("adam: master must be a 1-D fp32 tensor")
+    if not (0.0 <= beta1 < 1.0 and 0.0 <= beta2 < 1.0):
+        raise ValueError("adam: beta1 and beta2 must lie in [0, 1)")
+    if not (eps > 0.0 and math.isfinite(eps)):
+        raise ValueError(f"adam: eps must be finite and > 0, got {eps}")
+    if not (wd >= 0.0 and math.isfinite(wd)):
+        raise ValueError(f"adam: wd must be finite and >= 0, got {wd}")
+    if not 0.0 < grad_scale <= 1.0:
+        raise ValueError("adam: grad_scale must be 1 / contributors")
+
+
+def _f32(x) -> float:
+    import numpy as np
+    return float(np.float32(x))
+
+
+def _adam_decay(master, wd, offsets, numels, adapt_mask):
+    """wd on the tensors whose bit is set in adapt_mask, 0 elsewhere."""
+    if sum(int(m) for m in numels) != master.numel():
+        raise ValueError("adam: the segments must tile [0, n) in order")
+    per = torch.tensor([_f32(wd) if (adapt_mask >> t) & 1 else 0.0
+                        for t in range(len(offsets))], dtype=torch.float32)
+    return torch.repeat_interleave(per, torch.tensor(
+        [int(m) for m in numels])).to(master.device)
+
+
+def adam_moments(grad, m, v, grad_scale, beta1, beta2, eps, c1, c2,
+                 clip_coef=None, mask=None):
+    """m, v in place from gh = ((g * s) * coef) * mask; returns
+    u = (m / c1) / (sqrt(v / c2) + eps)."""
+    gh = grad.float() * _f32(grad_scale)
+    gh = gh * (clip_coef.float().reshape(()) if clip_coef is not None else 1.0)
+    if mask is not None:
+        gh = gh * mask
+    m.mul_(_f32(beta1)).add_(gh * _f32(1.0 - beta1))
+    v.mul_(_f32(beta2)).add_((gh * gh) * _f32(1.0 - beta2))
+    return adam_u(m, v, eps, c1, c2)
+
+
+def adam_u(m, v, eps, c1, c2):
+    # full tensors as divisors (torch may divide by a scalar through its
+    # reciprocal, which rounds twice) and numpy's correctly rounded sqrt
+    # (torch's vectorized CPU sqrt is not, in about 1 value of 100)
+    import numpy as np
+    vh = v / torch.full_like(v, float(c2))
+    root = torch.from_numpy(np.sqrt(vh.cpu().numpy())).to(v.device)
+    return (m / torch.full_like(m, float(c1))) / (root + _f32(eps))
+
+
+def _adam_publish(master, ema, ema_decay, offset, shadow):
+    if ema is not None:
+        ema.sub_((ema - master) * ema_weight(ema_decay, offset))
+    if shadow is not None:
+        shadow.copy_(master.to(shadow.dtype))
+
+
+def _dc_mask(n, drop_connect_keep, gen, mask, device):
+    if mask is None and drop_connect_keep is not None:
+        mask = (torch.rand(n, device=device, dtype=torch.float32,
+                           generator=gen) < drop_connect_keep).float()
+    return mask
+
+
+def adam_step(master, grad, m, v, lr: float, grad_scale: float = 1.0,
+              beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
+              wd: float = 0.0, offsets=None, numels=None, adapt_mask: int = 0,
+              drop_connect_keep=None, gen=None, mask=None, shadow=None,
+              ema=None, ema_decay: float = 0.0, offset: int = 0,
+              clip_coef=None):
+    """In-place Adam / AdamW update k = offset + 1 of the flat fp32 `master`
+    with the aggregated gradient `grad` (the SUM over contributors, grad_scale
+    = s = 1 / contributors):
+
+      gh = coef * s * g, then the drop-connect mask
+      m = b1*m + (1 - b1)*gh          v = b2*v + (1 - b2)*gh^2
+      u = (m / (1 - b1^k)) / (sqrt(v / (1 - b2^k)) + eps)
+      w -= lr * (u + wd_t * w)        wd_t = wd on the tensors of adapt_mask
+
+    then the moving average and the shadow as sgd_step does.  mask: an
+    explicit keep mask instead of one drawn from `gen`."""
+    _adam_check(master, beta1, beta2, eps, wd, grad_scale)
+    offsets = [0] if offsets is None else offsets
+    numels = [master.numel()] if numels is None else numels
+    lr32, c1, c2 = adam_constants(lr, grad_scale, beta1, beta2, offset)
+    mask = _dc_mask(master.numel(), drop_connect_keep, gen, mask,
+                    master.device)
+    u = adam_moments(grad, m, v, grad_scale, beta1, beta2, eps, c1, c2,
+                     clip_coef, mask)
+    u = u + _adam_decay(master, wd, offsets, numels, adapt_mask) * master
+    master.sub_(u * float(lr32))
+    _adam_publish(master, ema, ema_decay, offset, shadow)
+    return master
+
+
+def lamb_moments(master, grad, m, v, grad_scale: float, beta1: float,
+                 beta2: float, eps: float, wd: float, offsets, numels,
+                 adapt_mask: int, offset: int = 0, clip_coef=None,
+                 drop_connect_keep=None, gen=None, mask=None):
+    """LAMB pass 1: m, v in place (adam_step's), then per tensor the norms of
+    the master and of u_t = u + wd_t * w (sums in float64 from the fp32
+    values) and r_t = |w_t| / |u_t| for the tensors of adapt_mask with both
+    norms > 0, else 1.  Returns (lamb_tab [16], lamb_stats [3 * segments] =
+    (|w_t|, |u_t|, r_t))."""
+    import numpy as np
+    f32 = np.float32
+    _adam_check(master, beta1, beta2, eps, wd, grad_scale)
+    _, c1, c2 = adam_constants(0.0, grad_scale, beta1, beta2, offset)
+    mask = _dc_mask(master.numel(), drop_connect_keep, gen, mask,
+                    master.device)
+    u = adam_moments(grad, m, v, grad_scale, beta1, beta2, eps, c1, c2,
+                     clip_coef, mask)
+    u = u + _adam_decay(master, wd, offsets, numels, adapt_mask) * master
+    tab = np.ones(16, dtype=np.float32)
+    stats = np.zeros(3 * len(offsets), dtype=np.float32)
+    u64, w64 = u.double(), master.detach().double()
+    for t, (o, n) in enumerate(zip(offsets, numels)):
+        wn = f32(np.sqrt(float((w64[o:o + n] * w64[o:o + n]).sum())))
+        un = f32(np.sqrt(float((u64[o:o + n] * u64[o:o + n]).sum())))
+        if (adapt_mask >> t) & 1 and wn > 0 and un > 0:
+            tab[t] = wn / un
+        stats[3 * t:3 * t + 3] = (wn, un, tab[t])
+    dev = master.device
+    return torch.from_numpy(tab).to(dev), torch.from_numpy(stats).to(dev)
+
+
+def lamb_apply(master, m, v, lamb_tab, lr: float, grad_scale: float,
+               beta1: float, beta2: float, eps: float, wd: float, offsets,
+               numels, adapt_mask: int, offset: int = 0, shadow=None,
+               ema=None, ema_decay: float = 0.0):
+    """LAMB pass 2: w -= (lr * r_t) * u_t with u_t recomputed from the
+    moments lamb_moments left; then the moving average and the shadow."""
+    _adam_check(master, beta1, beta2, eps, wd, grad_scale)
+    lr32, c1, c2 = adam_constants(lr, grad_scale, beta1, beta2, offset)
+    u = adam_u(m, v, eps, c1, c2)
+    u = u + _adam_decay(master, wd, offsets, numels, adapt_mask) * master
+    lr_t = torch.repeat_interleave(
+        lamb_tab.float().cpu()[:len(offsets)] * float(lr32),
+        torch.tensor([int(n) for n in numels])).to(master.device)
+    master.sub_(u * lr_t)
+    _adam_publish(master, ema, ema_decay, offset, shadow)
+    return master
+
+
 def ema_weight(ema_decay: float, offset: int) -> float:
     """1 - d_k of update k = offset + 1, in numpy.float32 (the arithmetic
     of sgd_step_kernel_ema)."""

@@ -420,3 +420,106 @@ def sgd_step(master: torch.Tensor, grad: torch.Tensor, lr: float,
                          momentum=momentum, mu=mu, ema=ema,
                          ema_decay=ema_decay, offset=offset,
                          clip_coef=clip_coef, **lars)
+
+
+def _cpu_gen(drop_connect_keep, seed, offset):
+    if drop_connect_keep is None:
+        return None
+    gen = torch.Generator(device="cpu")
+    gen.manual_seed((seed * 0x9E3779B97F4A7C15 + offset) % (2**63))
+    return gen
+
+
+def adam_step(master: torch.Tensor, grad: torch.Tensor, m: torch.Tensor,
+              v: torch.Tensor, lr: float, grad_scale: float = 1.0,
+              beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
+              wd: float = 0.0, offsets=None, numels=None, adapt_mask: int = 0,
+              drop_connect_keep=None, seed: int = 0, offset: int = 0,
+              shadow=None, ema=None, ema_decay: float = 0.0, clip_coef=None,
+              lr_scale_dev=None, offset_dev=None, zero_grad: bool = False):
+    """Fused flat Adam / AdamW update k = offset + 1 (ops/cpu_ref.py::
+    adam_step): the moments `m`, `v` and `master` in place, decoupled decay
+    `wd` on the tensors (offsets, numels) whose bit is set in `adapt_mask`,
+    then the moving average and the bf16 shadow as sgd_step().  `grad` is the
+    SUM over contributors, grad_scale = 1 / contributors; `clip_coef`
+    multiplies it first.  On the GPU one adam_step_kernel launch; with
+    `lr_scale_dev` / `offset_dev` (fp32 lr * grad_scale and int64 offset on
+    the device) it is hipGraph-capturable, and `zero_grad` clears the bucket
+    in the same pass."""
+    if ema is not None and not 0.0 <= ema_decay < 1.0:
+        raise ValueError(f"ema_decay must lie in [0, 1), got {ema_decay}")
+    offsets = [0] if offsets is None else [int(o) for o in offsets]
+    numels = [master.numel()] if numels is None else [int(x) for x in numels]
+    if master.is_cuda:
+        _C.ext().adam_step(
+            master, grad, m, v, float(lr), float(grad_scale), float(beta1),
+            float(beta2), float(eps), float(wd), offsets, numels,
+            int(adapt_mask),
+            -1.0 if drop_connect_keep is None else float(drop_connect_keep),
+            int(seed), int(offset), shadow=shadow, ema=ema,
+            ema_decay=float(ema_decay), clip_coef=clip_coef,
+            lr_scale_dev=lr_scale_dev, offset_dev=offset_dev,
+            zero_grad=bool(zero_grad))
+    else:
+        cpu_ref.adam_step(master, grad, m, v, lr, grad_scale, beta1, beta2,
+                          eps, wd, offsets, numels, adapt_mask,
+                          drop_connect_keep,
+                          _cpu_gen(drop_connect_keep, seed, offset),
+                          shadow=shadow, ema=ema, ema_decay=ema_decay,
+                          offset=offset, clip_coef=clip_coef)
+        if zero_grad:
+            grad.zero_()
+    return master
+
+
+def lamb_step(master: torch.Tensor, grad: torch.Tensor, m: torch.Tensor,
+              v: torch.Tensor, lr: float, grad_scale: float, beta1: float,
+              beta2: float, eps: float, wd: float, offsets, numels,
+              adapt_mask: int, lamb_tab=None, lamb_stats=None,
+              drop_connect_keep=None, seed: int = 0, offset: int = 0,
+              shadow=None, ema=None, ema_decay: float = 0.0, clip_coef=None,
+              lr_scale_dev=None, offset_dev=None, zero_grad: bool = False):
+    """LAMB update k = offset + 1 (You et al. 2019; ops/cpu_ref.py::
+    lamb_moments + lamb_apply): Adam's moments, u_t = u + wd_t * w, the trust
+    ratio r_t = |w_t| / |u_t| of every tensor in `adapt_mask` (1 elsewhere
+    and for a zero norm), w -= lr * r_t * u_t.  `lamb_tab` (fp32 [16], r_t)
+    and `lamb_stats` (fp32 [3 * segments]: |w_t|, |u_t|, r_t) are written in
+    place when given.  On the GPU two launches and no host round trip:
+    lamb_moments_kernel (fixed-order reduction, no float atomics) and
+    lamb_apply_kernel; the other arguments as adam_step().  Returns
+    (lamb_tab, lamb_stats)."""
+    if ema is not None and not 0.0 <= ema_decay < 1.0:
+        raise ValueError(f"ema_decay must lie in [0, 1), got {ema_decay}")
+    offsets, numels = [int(o) for o in offsets], [int(x) for x in numels]
+    dev = master.device
+    if lamb_tab is None:
+        lamb_tab = torch.ones(16, dtype=torch.float32, device=dev)
+    if lamb_stats is None:
+        lamb_stats = torch.zeros(3 * len(offsets), dtype=torch.float32,
+                                 device=dev)
+    hp = (float(beta1), float(beta2), float(eps), float(wd), offsets, numels,
+          int(adapt_mask))
+    if master.is_cuda:
+        ext = _C.ext()
+        ext.lamb_moments(
+            master, grad, m, v, float(grad_scale), *hp,
+            -1.0 if drop_connect_keep is None else float(drop_connect_keep),
+            int(seed), int(offset), lamb_tab, lamb_stats,
+            clip_coef=clip_coef, offset_dev=offset_dev)
+        ext.lamb_apply(master, grad, m, v, float(lr), float(grad_scale), *hp,
+                       int(offset), lamb_tab, shadow=shadow, ema=ema,
+                       ema_decay=float(ema_decay), lr_scale_dev=lr_scale_dev,
+                       offset_dev=offset_dev, zero_grad=bool(zero_grad))
+    else:
+        tab, stats = cpu_ref.lamb_moments(
+            master, grad, m, v, grad_scale, *hp, offset=offset,
+            clip_coef=clip_coef, drop_connect_keep=drop_connect_keep,
+            gen=_cpu_gen(drop_connect_keep, seed, offset))
+        lamb_tab.copy_(tab)
+        lamb_stats.copy_(stats)
+        cpu_ref.lamb_apply(master, m, v, lamb_tab, lr, grad_scale, *hp,
+                           offset=offset, shadow=shadow, ema=ema,
+                           ema_decay=ema_decay)
+        if zero_grad:
+            grad.zero_()
+    return lamb_tab, lamb_stats

@@ -50,14 +50,44 @@ def _lars_eta(text: str) -> float:
     return v
 
 
+def _adam_eps(text: str) -> float:
+    """--adam_eps: finite and > 0."""
+    try:
+        v = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a number: {text!r}")
+    if not 0.0 < v < float("inf"):  # also refuses nan
+        raise argparse.ArgumentTypeError(
+            f"must be finite and > 0, got {text}")
+    return v
+
+
 class _TrainParser(argparse.ArgumentParser):
     """Checks that span two flags, reported as argument errors."""
 
     def parse_known_args(self, args=None, namespace=None):
         ns, rest = super().parse_known_args(args, namespace)
-        if ns.weight_decay > 0 and not ns.lars_eta > 0:
-            self.error("argument --weight_decay: needs --lars_eta > 0 (the "
-                       "decay is applied by the LARS update only)")
+        if ns.optimizer == "sgd":
+            if ns.weight_decay > 0 and not ns.lars_eta > 0:
+                self.error("argument --weight_decay: needs --lars_eta > 0 "
+                           "(the decay is applied by the LARS update only) "
+                           "or --optimizer adam|lamb")
+            for name in ("adam_beta1", "adam_beta2", "adam_eps"):
+                if getattr(ns, name) is not None:
+                    self.error(f"argument --{name}: needs --optimizer "
+                               "adam|lamb")
+        else:
+            if ns.momentum > 0:
+                self.error("argument --momentum: not with --optimizer "
+                           f"{ns.optimizer} (beta1 is its momentum)")
+            if ns.lars_eta > 0:
+                self.error("argument --lars_eta: not with --optimizer "
+                           f"{ns.optimizer} (lamb is the Adam-based LARS)")
+        # the defaults, once the "was it given" check is done
+        for name, default in (("adam_beta1", 0.9), ("adam_beta2", 0.999),
+                              ("adam_eps", 1e-8)):
+            if getattr(ns, name) is None:
+                setattr(ns, name, default)
         return ns, rest
 
 
@@ -215,7 +245,24 @@ def build_train_parser() -> argparse.ArgumentParser:
                    default=0.0, metavar="WD",
                    help="L2 weight decay of the LARS update (weight tensors "
                         "only): g += WD * w inside the trust ratio and the "
-                        "step. Needs --lars_eta")
+                        "step. Needs --lars_eta. With --optimizer adam: "
+                        "decoupled AdamW decay, w -= lr * WD * w; with "
+                        "--optimizer lamb: u += WD * w before the trust ratio")
+    p.add_argument("--optimizer", choices=("sgd", "adam", "lamb"),
+                   default="sgd",
+                   help="sgd: the fused SGD pass (--momentum, --lars_eta). "
+                        "adam: fused Adam / AdamW. lamb: LAMB (You et al. "
+                        "2019), Adam's update scaled per weight tensor by "
+                        "|w| / |update|, the norms reduced on the device in a "
+                        "fixed order; biases get plain Adam. Both keep two "
+                        "fp32 moment buffers (checkpointed as flat_adam_m / "
+                        "flat_adam_v); not with --momentum or --lars_eta")
+    p.add_argument("--adam_beta1", type=_decay, default=None, metavar="B1",
+                   help="first-moment decay in [0, 1) (default 0.9)")
+    p.add_argument("--adam_beta2", type=_decay, default=None, metavar="B2",
+                   help="second-moment decay in [0, 1) (default 0.999)")
+    p.add_argument("--adam_eps", type=_adam_eps, default=None, metavar="EPS",
+                   help="added to sqrt(v) (default 1e-8); finite and > 0")
     p.add_argument("--deterministic", action="store_true",
                    help="bitwise-reproducible gradients on the GPU: the fused "
                         "LeNet step reduces every weight and bias gradient "
