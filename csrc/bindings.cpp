@@ -499,6 +499,11 @@ std::vector<torch::Tensor> conv_pool_fwd(torch::Tensor x, torch::Tensor w,
     launch_conv1_direct_fwd(bf16_ptr(x), bf16_ptr(w), b.data_ptr<float>(),
                             bf16_mut(y), amax.data_ptr<uint8_t>(), NB, H, W,
                             Cout, s);
+  } else if (conv_slab_supported(H, W, Cin, Cout) &&
+             conv2_resident_route(CONV2_RES_FWD, NB)) {
+    // weights resident in LDS, one persistent block per CU
+    launch_conv2_fwd_resident(bf16_ptr(x), bf16_ptr(w), b.data_ptr<float>(),
+                              bf16_mut(y), amax.data_ptr<uint8_t>(), NB, s);
   } else if (conv_slab_supported(H, W, Cin, Cout)) {
     // per-image LDS slab: activations cross the fabric once (not 25x)
     launch_conv_fwd_slab(bf16_ptr(x), bf16_ptr(w), b.data_ptr<float>(),
@@ -928,10 +933,15 @@ torch::Tensor conv_dx_pooled(torch::Tensor gp, torch::Tensor am,
   CHECK_BF16(w); CHECK_CONTIG(w);
   TORCH_CHECK(Cin == 32 && w.numel() == 25 * 32 * 64,
               "conv_dx_pooled: LeNet conv2 shapes only");
-  TORCH_CHECK(force_db >= 0 && force_db <= 2, "force_db is 0, 1 or 2");
+  TORCH_CHECK(force_db >= 0 && force_db <= 3, "force_db is 0, 1, 2 or 3");
   int NB = gp.size(0);
   auto dx = torch::empty({NB, 14, 14, 32}, gp.options());
-  if (NB > 0)
+  // 3 forces the weight-resident persistent kernel, 0 takes it by NB
+  if (NB > 0 && (force_db == 3 ||
+                 (force_db == 0 && conv2_resident_route(CONV2_RES_DX, NB))))
+    launch_conv2_dx_resident(bf16_ptr(gp), am.data_ptr<uint8_t>(), bf16_ptr(w),
+                             bf16_mut(dx), NB, cur_stream());
+  else if (NB > 0)
     launch_conv_dx_slab_pooled(bf16_ptr(gp), am.data_ptr<uint8_t>(),
                                bf16_ptr(w), bf16_mut(dx), NB, (int)force_db,
                                cur_stream());
@@ -1869,6 +1879,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "conv2 dX from the pooled gradient + pool argmax bytes",
         py::arg("gp"), py::arg("am"), py::arg("w"), py::arg("Cin"),
         py::arg("force_db") = 0);
+  m.def("conv2_resident_route", [](int64_t op, int64_t NB) {
+          return conv2_resident_route((int)op, (int)NB);
+        }, "whether conv2 forward (op 0) / pooled dX (op 1) take the "
+           "weight-resident persistent kernel at batch NB",
+        py::arg("op"), py::arg("NB"));
   m.def("conv_dw_pooled_into", &conv_dw_pooled_into,
         "conv2 dW from the pooled gradient + pool argmax bytes, into bucket",
         py::arg("x"), py::arg("gp"), py::arg("am"), py::arg("dw_out"));

@@ -366,6 +366,23 @@ void launch_conv_dx_slab_pooled(const unsigned short* gp, const uint8_t* am,
 void launch_conv_dw_slab(const unsigned short* x, const unsigned short* dact,
                          float* dw, int NB, int H, int W, int Cin, int Cout,
                          hipStream_t);
+// conv2_resident.hip — persistent conv2 forward / pooled dX with the weights
+// resident in LDS (one block per CU walking images).  conv2_resident_route
+// is the one place that decides between them and the per-image slab kernels.
+// Default: dX resident from NB >= CONV2_RES_MIN_NB, forward per-image (it
+// does not pay inside the step).  DMNIST_CONV2_RESIDENT=0|fwd|dx|both picks
+// the ops, DMNIST_CONV2_RES_MIN_NB=n replaces the tier (tests, sweeps); other
+// values of either throw.  profiles/conv2_resident_b1024_b8192.md.
+enum { CONV2_RES_FWD = 0, CONV2_RES_DX = 1 };
+constexpr int CONV2_RES_MIN_NB = 64;       // smallest NB measured; ahead there
+constexpr int CONV2_RES_WAVES = 8;         // waves per block (4 | 8)
+bool conv2_resident_route(int op, int NB);
+void launch_conv2_fwd_resident(const unsigned short* x, const unsigned short* w,
+                               const float* bias, unsigned short* y,
+                               uint8_t* amax, int NB, hipStream_t);
+void launch_conv2_dx_resident(const unsigned short* gp, const uint8_t* am,
+                              const unsigned short* w, unsigned short* dx,
+                              int NB, hipStream_t);
 bool conv1_slab_supported(int H, int W, int Cin, int Cout);
 void launch_conv1_dw_slab(const unsigned short* x, const unsigned short* dact,
                           float* dw, int NB, int H, int W, int Cout,

@@ -63,11 +63,26 @@ class FusedLeNetStep:
         elif _os.environ.get("DMNIST_SINGLE_STREAM"):
             self.overlap_level = 0
         else:
-            self.overlap_level = 0 if t.flags.batch_size < 4096 else 2
+            self.overlap_level = None   # by batch and conv2 dX route, below
         self.single_stream = self.overlap_level == 0
         # pool2 backward inside the conv2 dX / dW staging (gp2 + am2, no
         # dense dact2); DMNIST_POOL2_FUSED=0 keeps the dX+unpool route
         self.pool2_fused = _os.environ.get("DMNIST_POOL2_FUSED", "1") != "0"
+        if self.overlap_level is None:
+            # the weight-resident conv2 dX block fills its CU's LDS, so a
+            # side-stream conv2 dW block finds no room next to it: where that
+            # kernel runs the single stream wins at every batch size (0.593
+            # vs 0.641 ms at B=4096, 1.049 vs 1.182 at B=8192,
+            # profiles/conv2_resident_b1024_b8192.md).  It runs only on the
+            # pooled route (DMNIST_POOL2_FUSED=0 goes through the dense
+            # conv_dx).  Like the rest of the schedule this is fixed when the
+            # step is built, from the switches as they stand then; the
+            # kernel route itself is re-read on every call.
+            resident_dx = self.pool2_fused and self.ext.conv2_resident_route(
+                1, t.flags.batch_size)
+            self.overlap_level = (0 if t.flags.batch_size < 4096 or resident_dx
+                                  else 2)
+            self.single_stream = self.overlap_level == 0
         # side stream resolved PER CALL: in single-stream mode it must be
         # whatever stream the body is running on RIGHT NOW (warmup and
         # graph capture run on their own streams — freezing the init-time
