@@ -1531,6 +1531,149 @@ void lamb_apply(torch::Tensor master, torch::Tensor grad, torch::Tensor am,
                     cur_stream());
 }
 
+// ---- Muon (muon.hip) -------------------------------------------------------
+// The per-device workspace of the kernel sequence: the bf16 matrices (u / X of
+// every weight tensor, the tiled route's second X, G and P), the fp32 Gram
+// planes, and the reduction state (s_t table, partials, ticket).  Allocated
+// at the first call and when a larger layout arrives, outside graph capture.
+struct MuonWorkspace {
+  torch::Tensor bf, planes, red;
+};
+constexpr int64_t kMuonRed =
+    GRAD_NORM_MAX_SEGS + GRAD_NORM_MAX_SEGS * GRAD_NORM_MAX_BLOCKS + 1;
+
+static MuonWorkspace& muon_workspace(const torch::Tensor& like,
+                                     const MuonPlan& pl, hipStream_t s) {
+  static auto* slots = new std::vector<MuonWorkspace>(64);
+  const int dev = like.get_device();
+  TORCH_CHECK(dev >= 0 && dev < (int)slots->size(), "muon: bad device index");
+  MuonWorkspace& w = (*slots)[dev];
+  const int64_t planes = std::max<int64_t>(1, pl.plane_floats);
+  if (!w.bf.defined() || w.bf.numel() < pl.bf16_elems ||
+      w.planes.numel() < planes) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    hipStreamIsCapturing(s, &cap);
+    TORCH_CHECK(cap == hipStreamCaptureStatusNone,
+                "muon: first call on a device allocates its workspace and "
+                "must run outside graph capture");
+    w.bf = torch::empty({pl.bf16_elems},
+                        like.options().dtype(at::kBFloat16));
+    w.planes = torch::empty({planes}, like.options().dtype(at::kFloat));
+    if (!w.red.defined())
+      w.red = torch::zeros({kMuonRed}, like.options().dtype(at::kFloat));
+  }
+  return w;
+}
+
+static MuonPlan muon_plan_checked(const char* who, const GradNormSegs& segs,
+                                  const std::vector<int64_t>& cols,
+                                  unsigned adapt, int force_route) {
+  TORCH_CHECK((int)cols.size() == segs.n, who, ": one cols entry per segment");
+  int c[GRAD_NORM_MAX_SEGS] = {};
+  for (int t = 0; t < segs.n; ++t) {
+    TORCH_CHECK(cols[t] >= 1 && cols[t] <= (int64_t(1) << 24), who,
+                ": cols must be >= 1");
+    c[t] = (int)cols[t];
+  }
+  MuonPlan pl;
+  int bad = -1;
+  TORCH_CHECK(muon_plan(segs, c, adapt, force_route, &pl, &bad), who,
+              ": segment ", bad, " ([", bad >= 0 ? segs.len[bad] / c[bad] : 0,
+              "][", bad >= 0 ? c[bad] : 0, "]) fits ",
+              force_route == MUON_LDS ? "not in one workgroup's LDS (cols <= "
+                                        "64 and the padded matrix in 160 KB)"
+              : force_route == MUON_TILED
+                  ? "not the tiled route (cols % 64 == 0, cols <= 512, "
+                    "rows % 8 == 0)"
+                  : "neither the LDS route (cols <= 64) nor the tiled route "
+                    "(cols % 64 == 0, cols <= 512, rows % 8 == 0)");
+  return pl;
+}
+
+void muon_step(torch::Tensor master, torch::Tensor grad, torch::Tensor mom,
+               double lr, double scale, double mu, double wd,
+               std::vector<int64_t> offsets, std::vector<int64_t> numels,
+               std::vector<int64_t> cols, int64_t adapt_mask, double dc_keep,
+               int64_t seed, int64_t offset, int64_t iters,
+               c10::optional<torch::Tensor> shadow,
+               c10::optional<torch::Tensor> ema, double ema_decay,
+               c10::optional<torch::Tensor> clip_coef,
+               c10::optional<torch::Tensor> lr_scale_dev,
+               c10::optional<torch::Tensor> offset_dev, bool zero_grad) {
+  // adam_call's checks of the flat streams, the scale and the device scalars
+  AdamCall c = adam_call("muon_step", master, {&grad, &mom}, lr, scale, 0.0,
+                         0.0, 1.0, wd, offsets, numels, adapt_mask, dc_keep,
+                         seed, lr_scale_dev, offset_dev);
+  TORCH_CHECK(mu >= 0.0 && mu < 1.0, "muon_step: mu must lie in [0, 1)");
+  TORCH_CHECK(iters >= 1 && iters <= 16, "muon_step: iters in 1..16");
+  const MuonPlan pl = muon_plan_checked("muon_step", c.segs, cols,
+                                        (unsigned)adapt_mask, MUON_NONE);
+  auto s = cur_stream();
+  MuonWorkspace& w = muon_workspace(master, pl, s);
+  unsigned short* ws = bf16_mut(w.bf);
+  float* tab = w.red.data_ptr<float>();
+  float* part = tab + GRAD_NORM_MAX_SEGS;
+  unsigned* ticket = reinterpret_cast<unsigned*>(
+      part + GRAD_NORM_MAX_SEGS * GRAD_NORM_MAX_BLOCKS);
+  const MuonArgs a{mu, wd, (float)scale, (unsigned)adapt_mask, (float)dc_keep,
+                   (uint64_t)seed};
+  launch_muon_momentum(grad.data_ptr<float>(), mom.data_ptr<float>(), ws, c.n,
+                       c.segs, pl, a, (uint64_t)offset, c.offset_dev,
+                       clip_coef_ptr(clip_coef, master), tab, part, ticket, s);
+  const unsigned short* out[GRAD_NORM_MAX_SEGS] = {};
+  launch_muon_ns(pl, ws, w.planes.data_ptr<float>(), tab, (int)iters, out, s);
+  launch_muon_update(master.data_ptr<float>(), grad.data_ptr<float>(),
+                     mom.data_ptr<float>(), adam_shadow(shadow, master), c.n,
+                     c.segs, pl, out, a, c.lr_scale, (uint64_t)offset,
+                     c.lr_scale_dev, c.offset_dev, zero_grad ? 1 : 0,
+                     ema_ptr(ema, master, ema_decay), (float)ema_decay, s);
+}
+
+// One matrix through the momentum pass (mu = 0: u = x, s = 1 / (|x| + 1e-7))
+// and `iters` Newton-Schulz iterations on the chosen route; for tests and
+// tools (it allocates per call).
+torch::Tensor muon_orthogonalize(torch::Tensor x, int64_t iters,
+                                 std::string route) {
+  CHECK_CUDA(x);
+  TORCH_CHECK(x.dim() == 2 && x.numel() >= 1 &&
+              (x.scalar_type() == at::kFloat ||
+               x.scalar_type() == at::kBFloat16),
+              "muon_orthogonalize: x is a non-empty fp32 or bf16 matrix");
+  TORCH_CHECK(iters >= 1 && iters <= 16, "muon_orthogonalize: iters in 1..16");
+  TORCH_CHECK(route == "auto" || route == "lds" || route == "tiled",
+              "muon_orthogonalize: route is auto, lds or tiled");
+  const int force = route == "lds" ? MUON_LDS
+                    : route == "tiled" ? MUON_TILED : MUON_NONE;
+  torch::Tensor g = x.to(at::kFloat).contiguous().reshape({-1});
+  if (reinterpret_cast<uintptr_t>(g.data_ptr()) % 16 != 0) g = g.clone();
+  const int64_t n = g.numel();
+  GradNormSegs segs = tiling_segs("muon_orthogonalize", std::vector<int64_t>{0},
+                                  std::vector<int64_t>{n}, n);
+  const MuonPlan pl = muon_plan_checked("muon_orthogonalize", segs,
+                                        std::vector<int64_t>{x.size(1)}, 1u,
+                                        force);
+  auto s = cur_stream();
+  torch::Tensor mom = torch::zeros_like(g);
+  torch::Tensor bf = torch::empty({pl.bf16_elems},
+                                  g.options().dtype(at::kBFloat16));
+  torch::Tensor planes = torch::empty(
+      {std::max<int64_t>(1, pl.plane_floats)}, g.options());
+  static auto* red_ws = new WorkspaceSlots(64);
+  float* tab = device_workspace(
+      *red_ws, g, kMuonRed, at::kFloat, s, "muon_orthogonalize",
+      "muon_orthogonalize: not inside graph capture").data_ptr<float>();
+  float* part = tab + GRAD_NORM_MAX_SEGS;
+  unsigned* ticket = reinterpret_cast<unsigned*>(
+      part + GRAD_NORM_MAX_SEGS * GRAD_NORM_MAX_BLOCKS);
+  const MuonArgs a{0.0, 0.0, 1.f, 1u, -1.f, 0};
+  unsigned short* ws = bf16_mut(bf);
+  launch_muon_momentum(g.data_ptr<float>(), mom.data_ptr<float>(), ws, n,
+                       segs, pl, a, 0, nullptr, nullptr, tab, part, ticket, s);
+  const unsigned short* out[GRAD_NORM_MAX_SEGS] = {};
+  launch_muon_ns(pl, ws, planes.data_ptr<float>(), tab, (int)iters, out, s);
+  return bf.narrow(0, out[0] - ws, n).view({x.size(0), x.size(1)}).clone();
+}
+
 void ema_publish(torch::Tensor ema, torch::Tensor shadow,
                  std::vector<int64_t> offsets, std::vector<int64_t> rows,
                  std::vector<int64_t> cols, std::vector<torch::Tensor> dsts) {
@@ -2006,6 +2149,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           return std::make_tuple(blocks, chain);
         }, "(blocks, chain) of lamb_moments on n elements: grad_norm's grid; "
         "each of the two sums is a chain of that length");
+  m.def("muon_step", &muon_step,
+        "Muon update of the flat bucket: Nesterov momentum in `mom`, the "
+        "weight tensors of adapt_mask (row-major [numel / cols][cols]) "
+        "orthogonalised by `iters` Newton-Schulz iterations on MFMA, decoupled "
+        "decay, heavy-ball momentum on the biases; the moving average, the "
+        "bf16 shadow, the cleared bucket; lr_scale_dev + offset_dev make it "
+        "hipGraph-capturable after a first call outside capture",
+        py::arg("master"), py::arg("grad"), py::arg("mom"), py::arg("lr"),
+        py::arg("scale"), py::arg("mu"), py::arg("wd"), py::arg("offsets"),
+        py::arg("numels"), py::arg("cols"), py::arg("adapt_mask"),
+        py::arg("dc_keep"), py::arg("seed"), py::arg("offset"),
+        py::arg("iters") = 5, py::arg("shadow") = c10::nullopt,
+        py::arg("ema") = c10::nullopt, py::arg("ema_decay") = 0.0,
+        py::arg("clip_coef") = c10::nullopt,
+        py::arg("lr_scale_dev") = c10::nullopt,
+        py::arg("offset_dev") = c10::nullopt, py::arg("zero_grad") = false);
+  m.def("muon_orthogonalize", &muon_orthogonalize,
+        "bf16 Newton-Schulz orthogonalisation of one fp32 / bf16 [rows][cols] "
+        "matrix: X0 = x / (|x| + 1e-7), `iters` iterations on the LDS route, "
+        "the tiled route or the one the trainer would pick",
+        py::arg("x"), py::arg("iters") = 5, py::arg("route") = "auto");
   m.def("ema_publish", &ema_publish,
         "flat fp32 parameters -> flat bf16 shadow + transposed bf16 copies "
         "of the [rows][cols] slices at `offsets`, one launch",

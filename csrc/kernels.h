@@ -211,6 +211,66 @@ void launch_lamb_apply(float* master, float* grad, const float* am,
                        const float* lr_scale_dev, const long* offset_dev,
                        int zero_grad, float* ema, float ema_decay,
                        const float* lamb_tab, hipStream_t);
+// muon.hip — Muon (--optimizer muon): Nesterov momentum, per weight matrix
+// replaced by its Newton-Schulz orthogonalisation on the matrix cores
+// (docs/KERNELS.md "Muon").  A weight tensor (bit t of adapt) is the row-major
+// [len / cols][cols] view of its segment and takes one of two routes:
+// MUON_LDS (cols <= 64 and the padded matrix fits one workgroup's LDS) or
+// MUON_TILED (cols % 64 == 0, cols <= MUON_MAX_COLS, rows % 8 == 0).
+// muon_plan lays the bf16 workspace out (u / X per tensor, the second X of
+// the tiled tensors, G, P) and sizes the fp32 Gram planes; force_route =
+// MUON_NONE picks LDS where it fits, else tiled.  It returns false, with *bad
+// the segment, for a weight tensor that fits no (or not the forced) route.
+#define MUON_MAX_COLS 512
+#define MUON_MAX_SPLIT 16  // row slices of the tiled Gram matrix at most
+enum { MUON_NONE = 0, MUON_LDS = 1, MUON_TILED = 2 };
+struct MuonPlan {
+  int n;
+  int route[GRAD_NORM_MAX_SEGS];
+  int rows[GRAD_NORM_MAX_SEGS], cols[GRAD_NORM_MAX_SEGS];
+  long uoff[GRAD_NORM_MAX_SEGS];   // bf16 element offsets into the workspace,
+  long x2off[GRAD_NORM_MAX_SEGS];  // -1 where the tensor has no such matrix
+  float scale[GRAD_NORM_MAX_SEGS];  // 0.2 * sqrt(max(rows, cols))
+  long goff, poff;    // G and P of the tiled route
+  long bf16_elems;    // the whole bf16 workspace
+  long plane_floats;  // the fp32 Gram planes
+};
+struct MuonArgs {
+  double mu, wd;
+  float grad_scale;
+  unsigned adapt;
+  float dc_keep;
+  uint64_t seed;
+};
+bool muon_lds_fits(int rows, int cols);
+bool muon_tiled_fits(int rows, int cols);
+int muon_gram_split(int rows, int cols, int* kslice);  // slices, rows of each
+bool muon_plan(const GradNormSegs& segs, const int* cols, unsigned adapt,
+               int force_route, MuonPlan* plan, int* bad);
+// pass 1: mom = mu*mom + g in place, bf16(u = g + mu*mom) of the weight
+// tensors into ws, STORED tab[t] = 1 / (|u_t| + 1e-7) (GRAD_NORM_MAX_SEGS
+// floats; 0 for a bias).  part/ticket: a workspace of its own, sized like
+// grad_norm's.
+void launch_muon_momentum(const float* grad, float* mom, unsigned short* ws,
+                          long n, const GradNormSegs& segs,
+                          const MuonPlan& plan, const MuonArgs& a,
+                          uint64_t offset, const long* offset_dev,
+                          const float* clip_coef_dev, float* tab, float* part,
+                          unsigned* ticket, hipStream_t);
+// `iters` Newton-Schulz iterations of every weight tensor; out[t] = where the
+// result of tensor t lies in ws (nullptr for a bias)
+void launch_muon_ns(const MuonPlan& plan, unsigned short* ws, float* planes,
+                    const float* tab, int iters, const unsigned short** out,
+                    hipStream_t);
+// the final pass: master, the average, the shadow, (zero_grad) the bucket
+void launch_muon_update(float* master, float* grad, const float* mom,
+                        unsigned short* shadow, long n,
+                        const GradNormSegs& segs, const MuonPlan& plan,
+                        const unsigned short* const* out, const MuonArgs& a,
+                        float lr_scale, uint64_t offset,
+                        const float* lr_scale_dev, const long* offset_dev,
+                        int zero_grad, float* ema, float ema_decay,
+                        hipStream_t);
 // ema != nullptr (both launchers): the same pass also moves the fp32 moving
 // average towards the new master, e -= (1 - d_k)*(e - w) with
 // d_k = min(ema_decay, (1 + k)/(10 + k)), k = offset + 1 (a second

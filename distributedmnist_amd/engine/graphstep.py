@@ -343,9 +343,11 @@ class GraphedStep:
         # zero_grad=True: the bucket is cleared in the same pass that
         # consumes it — no per-step fill kernel in the replayed graph
         if getattr(t, "optimizer", "sgd") != "sgd":
-            # adam_step_kernel, or LAMB's two launches (the first call of
-            # lamb_moments, in the warmup, allocates its workspace); lr and
-            # the update count are read on the device
+            # adam_step_kernel, LAMB's two launches or Muon's kernel
+            # sequence (the first call of lamb_moments / muon_step, in the
+            # warmup, allocates its workspace; Muon's momentum is rolled back
+            # with flat_momentum above); lr and the update count are read on
+            # the device
             t.adam_update(fp.flat_grad, 0.0, self.inv_contrib,
                           self.dc_keep if self.dc_keep > 0 else None, 0,
                           clip_coef, lr_scale_dev=self.lr_scale_dev,

@@ -186,8 +186,11 @@ class Trainer:
         self._eager_fused_tried = False
         self._step_dev = None
         self._resident_ds = None  # DeviceDataSet (attach_dataset)
+        # --optimizer muon keeps its Nesterov momentum here at any mu
         self.flat_momentum = (torch.zeros_like(self.fp.flat_master)
-                              if flags.momentum > 0 else None)
+                              if flags.momentum > 0
+                              or getattr(flags, "optimizer", "sgd") == "muon"
+                              else None)
         # parameter-init parity across ranks (broadcast once)
         if world > 1 and dist.is_initialized():
             dist.broadcast(self.fp.flat_master, src=0)
@@ -259,16 +262,38 @@ class Trainer:
         # the tensors with dim() > 1 (the set LARS adapts), plain Adam on the
         # biases.  Every rank holds the same master and bucket: no collective.
         self.optimizer = getattr(flags, "optimizer", "sgd") or "sgd"
-        if self.optimizer not in ("sgd", "adam", "lamb"):
-            raise ValueError(f"--optimizer must be sgd, adam or lamb, got "
-                             f"{self.optimizer}")
-        if self.optimizer != "sgd" and (flags.momentum > 0
-                                        or self.lars_eta > 0):
+        if self.optimizer not in ("sgd", "adam", "lamb", "muon"):
+            raise ValueError(f"--optimizer must be sgd, adam, lamb or muon, "
+                             f"got {self.optimizer}")
+        if self.optimizer in ("adam", "lamb") and (flags.momentum > 0
+                                                   or self.lars_eta > 0):
             raise ValueError(f"--optimizer {self.optimizer} cannot be "
                              "combined with --momentum or --lars_eta")
         self.flat_adam_m = self.flat_adam_v = None
         self.lamb_tab = None
-        if self.optimizer != "sgd":
+        if self.optimizer == "muon":
+            # Muon (ops.functional.muon_step): Nesterov momentum in
+            # flat_momentum (checkpointed as for SGD; no new key), every
+            # tensor with dim() > 1 viewed as [numel / shape[-1]][shape[-1]]
+            # and moved along the Newton-Schulz orthogonalisation of its
+            # update, decoupled --weight_decay; biases get heavy-ball momentum
+            if self.lars_eta > 0:
+                raise ValueError("--optimizer muon cannot be combined with "
+                                 "--lars_eta")
+            if not 0.0 <= flags.momentum < 1.0:
+                raise ValueError("--momentum must lie in [0, 1) with "
+                                 f"--optimizer muon, got {flags.momentum}")
+            if len(self.fp.names) > 16:
+                raise ValueError("--optimizer muon supports at most 16 "
+                                 "parameter tensors")
+            self.muon = dict(
+                mu=float(flags.momentum), wd=self.weight_decay,
+                offsets=self.fp.offsets, numels=self.fp.numels,
+                cols=[int(p.shape[-1]) for p in self.fp.params], adapt_mask=0)
+            for i, p in enumerate(self.fp.params):
+                if p.dim() > 1:
+                    self.muon["adapt_mask"] |= 1 << i
+        elif self.optimizer != "sgd":
             if len(self.fp.names) > 16:
                 raise ValueError(f"--optimizer {self.optimizer} supports at "
                                  "most 16 parameter tensors")
@@ -588,9 +613,17 @@ class Trainer:
 
     def adam_update(self, grad, lr, grad_scale, dc_keep, offset, clip_coef,
                     **dev):
-        """The --optimizer adam|lamb update of one aggregated gradient.
+        """The --optimizer adam|lamb|muon update of one aggregated gradient.
         dev: lr_scale_dev, offset_dev, zero_grad of the graph-captured tail
         (lr and offset are then read on the device)."""
+        if self.optimizer == "muon":
+            Fx.muon_step(self.fp.flat_master, grad, self.flat_momentum, lr,
+                         grad_scale, drop_connect_keep=dc_keep,
+                         seed=self.flags.seed, offset=offset,
+                         shadow=self.fp.flat_shadow, ema=self.flat_ema,
+                         ema_decay=self.ema_decay, clip_coef=clip_coef,
+                         **self.muon, **dev)
+            return
         kw = dict(self.adam, drop_connect_keep=dc_keep, seed=self.flags.seed,
                   offset=offset, shadow=self.fp.flat_shadow,
                   ema=self.flat_ema, ema_decay=self.ema_decay,

@@ -527,6 +527,108 @@ def lamb_apply(master, m, v, lamb_tab, lr: float, grad_scale: float,
     return master
 
 
+# ---------------------------------------------------------------------------
+# Muon (--optimizer muon; csrc/muon.hip): Nesterov momentum whose per-matrix
+# update is replaced by its Newton-Schulz orthogonalisation.  The rounding
+# points are the kernels': X, G and P are bf16, products take bf16 operands
+# and accumulate in fp32, the polynomial and a*X + X P are fp32 on the
+# accumulator before the one rounding; the elementwise parts are one torch op
+# per fp32 operation, in the kernels' order.
+# ---------------------------------------------------------------------------
+MUON_ABC = (3.4445, -4.7750, 2.0315)
+
+
+def _bf16(x):
+    return x.to(torch.bfloat16).float()
+
+
+def muon_orthogonalize(x, iters: int = 5):
+    """`iters` Newton-Schulz iterations of the [rows][cols] matrix `x`
+    (fp32 or bf16) -> bf16, the arithmetic of csrc/muon.hip:
+
+      X = bf16(x), s = 1 / (|x|_F + 1e-7)   (the sum in float64, then fp32)
+      G = bf16(sc^2 * X^T X), P = bf16(b*G + c * G G),
+      X = bf16(sc * (a*X + X P))
+
+    with sc = s in the first iteration and 1 after it, so that X0 = s * X is
+    never rounded on its own.  The Gram matrix is on the column side; the
+    polynomial is odd, so this is right for rows < cols too."""
+    import numpy as np
+    f32 = np.float32
+    if x.dim() != 2 or not iters >= 1:
+        raise ValueError("muon_orthogonalize: x is a matrix, iters >= 1")
+    a, b, c = (_f32(v) for v in MUON_ABC)
+    xf = x.detach().float()
+    norm = f32(np.sqrt(float((xf.double() * xf.double()).sum())))
+    sc = float(f32(1) / (norm + f32(1e-7)))
+    X = _bf16(xf)
+    for _ in range(int(iters)):
+        G = _bf16((X.t() @ X) * _f32(sc * sc))
+        P = _bf16(G * b + (G @ G) * c)
+        X = _bf16((X * a + X @ P) * sc)
+        sc = 1.0
+    return X.to(torch.bfloat16)
+
+
+def muon_scale(rows: int, cols: int) -> float:
+    """0.2 * sqrt(max(rows, cols)): the update RMS of Adam, in fp32."""
+    return _f32(0.2 * math.sqrt(max(rows, cols)))
+
+
+def muon_step(master, grad, mom, lr: float, grad_scale: float = 1.0,
+              mu: float = 0.95, wd: float = 0.0, offsets=None, numels=None,
+              cols=None, adapt_mask: int = 0, drop_connect_keep=None,
+              gen=None, mask=None, shadow=None, ema=None,
+              ema_decay: float = 0.0, offset: int = 0, clip_coef=None,
+              iters: int = 5):
+    """In-place Muon update k = offset + 1 of the flat fp32 `master` with the
+    aggregated gradient `grad` (the SUM over contributors, grad_scale = s =
+    1 / contributors) and the momentum buffer `mom`:
+
+      gh = coef * s * g, then the drop-connect mask
+      v = mu*v + gh                 u = gh + mu*v
+      weight tensor t (bit t of adapt_mask), viewed [numel / cols[t]][cols[t]]:
+        w = w*(1 - lr*wd) - (lr * muon_scale(rows, cols)) * orthogonalize(u)
+      bias: w -= lr*v
+
+    then the moving average and the shadow as sgd_step does."""
+    import numpy as np
+    f32 = np.float32
+    if master.dtype != torch.float32 or master.dim() != 1:
+        raise ValueError("muon: master must be a 1-D fp32 tensor")
+    if not 0.0 <= mu < 1.0:
+        raise ValueError(f"muon: mu must lie in [0, 1), got {mu}")
+    if not (wd >= 0.0 and math.isfinite(wd)):
+        raise ValueError(f"muon: wd must be finite and >= 0, got {wd}")
+    if not 0.0 < grad_scale <= 1.0:
+        raise ValueError("muon: grad_scale must be 1 / contributors")
+    offsets = [0] if offsets is None else offsets
+    numels = [master.numel()] if numels is None else numels
+    if sum(int(m) for m in numels) != master.numel():
+        raise ValueError("muon: the segments must tile [0, n) in order")
+    lr32 = f32(lr * grad_scale) * f32(round(1.0 / grad_scale))
+    decay = float(f32(1) - lr32 * f32(wd))
+    mask = _dc_mask(master.numel(), drop_connect_keep, gen, mask,
+                    master.device)
+    gh = grad.float() * _f32(grad_scale)
+    gh = gh * (clip_coef.float().reshape(()) if clip_coef is not None else 1.0)
+    if mask is not None:
+        gh = gh * mask
+    mom.mul_(_f32(mu)).add_(gh)
+    u = gh + mom * _f32(mu)
+    for t, (o, n) in enumerate(zip(offsets, numels)):
+        w = master[o:o + n]
+        if (adapt_mask >> t) & 1:
+            c = int(cols[t])
+            x = muon_orthogonalize(u[o:o + n].view(n // c, c), iters)
+            step = float(lr32 * f32(muon_scale(n // c, c)))
+            w.mul_(decay).sub_(x.float().reshape(-1) * step)
+        else:
+            w.sub_(mom[o:o + n] * float(lr32))
+    _adam_publish(master, ema, ema_decay, offset, shadow)
+    return master
+
+
 def ema_weight(ema_decay: float, offset: int) -> float:
     """1 - d_k of update k = offset + 1, in numpy.float32 (the arithmetic
     of sgd_step_kernel_ema)."""

@@ -523,3 +523,56 @@ def lamb_step(master: torch.Tensor, grad: torch.Tensor, m: torch.Tensor,
         if zero_grad:
             grad.zero_()
     return lamb_tab, lamb_stats
+
+
+def muon_orthogonalize(x: torch.Tensor, iters: int = 5, route: str = "auto"):
+    """bf16 Newton-Schulz orthogonalisation of one [rows][cols] matrix
+    (ops/cpu_ref.py::muon_orthogonalize).  On the GPU `route` picks the
+    kernels: "lds" (muon_ns_lds_kernel: cols <= 64, the matrix resident in
+    one workgroup's LDS), "tiled" (the Gram / polynomial / apply kernels:
+    cols % 64 == 0, rows % 8 == 0) or "auto", the trainer's choice; a route
+    the shape does not fit is an error."""
+    if x.is_cuda:
+        return _C.ext().muon_orthogonalize(x, int(iters), str(route))
+    if route not in ("auto", "lds", "tiled"):
+        raise ValueError("muon_orthogonalize: route is auto, lds or tiled")
+    return cpu_ref.muon_orthogonalize(x, iters)
+
+
+def muon_step(master: torch.Tensor, grad: torch.Tensor, mom: torch.Tensor,
+              lr: float, grad_scale: float, mu: float, wd: float, offsets,
+              numels, cols, adapt_mask: int, drop_connect_keep=None,
+              seed: int = 0, offset: int = 0, shadow=None, ema=None,
+              ema_decay: float = 0.0, clip_coef=None, lr_scale_dev=None,
+              offset_dev=None, zero_grad: bool = False, iters: int = 5):
+    """Muon update k = offset + 1 (ops/cpu_ref.py::muon_step): Nesterov
+    momentum in `mom`; every tensor of `adapt_mask`, viewed as
+    [numel / cols[t]][cols[t]], moves along the Newton-Schulz orthogonalisation
+    of its update, scaled by 0.2 * sqrt(max(rows, cols)), with decoupled decay
+    `wd`; the biases take plain heavy-ball momentum.  On the GPU the kernel
+    sequence of csrc/muon.hip (momentum pass, one LDS-resident launch for the
+    narrow tensors, four launches per iteration for each tiled one, the update
+    pass), device-resident and hipGraph-capturable after a first call outside
+    capture; the other arguments as adam_step()."""
+    if ema is not None and not 0.0 <= ema_decay < 1.0:
+        raise ValueError(f"ema_decay must lie in [0, 1), got {ema_decay}")
+    offsets, numels = [int(o) for o in offsets], [int(x) for x in numels]
+    cols = [int(c) for c in cols]
+    if master.is_cuda:
+        _C.ext().muon_step(
+            master, grad, mom, float(lr), float(grad_scale), float(mu),
+            float(wd), offsets, numels, cols, int(adapt_mask),
+            -1.0 if drop_connect_keep is None else float(drop_connect_keep),
+            int(seed), int(offset), iters=int(iters), shadow=shadow, ema=ema,
+            ema_decay=float(ema_decay), clip_coef=clip_coef,
+            lr_scale_dev=lr_scale_dev, offset_dev=offset_dev,
+            zero_grad=bool(zero_grad))
+    else:
+        cpu_ref.muon_step(master, grad, mom, lr, grad_scale, mu, wd, offsets,
+                          numels, cols, adapt_mask, drop_connect_keep,
+                          _cpu_gen(drop_connect_keep, seed, offset),
+                          shadow=shadow, ema=ema, ema_decay=ema_decay,
+                          offset=offset, clip_coef=clip_coef, iters=iters)
+        if zero_grad:
+            grad.zero_()
+    return master

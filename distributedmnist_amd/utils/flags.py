@@ -76,6 +76,18 @@ class _TrainParser(argparse.ArgumentParser):
                 if getattr(ns, name) is not None:
                     self.error(f"argument --{name}: needs --optimizer "
                                "adam|lamb")
+        elif ns.optimizer == "muon":
+            # --momentum (its mu) and --weight_decay (decoupled) are legal
+            if not 0.0 <= ns.momentum < 1.0:
+                self.error("argument --momentum: must lie in [0, 1) with "
+                           "--optimizer muon")
+            if ns.lars_eta > 0:
+                self.error("argument --lars_eta: not with --optimizer muon "
+                           "(its update has a fixed norm per tensor)")
+            for name in ("adam_beta1", "adam_beta2", "adam_eps"):
+                if getattr(ns, name) is not None:
+                    self.error(f"argument --{name}: needs --optimizer "
+                               "adam|lamb")
         else:
             if ns.momentum > 0:
                 self.error("argument --momentum: not with --optimizer "
@@ -246,9 +258,10 @@ def build_train_parser() -> argparse.ArgumentParser:
                    help="L2 weight decay of the LARS update (weight tensors "
                         "only): g += WD * w inside the trust ratio and the "
                         "step. Needs --lars_eta. With --optimizer adam: "
-                        "decoupled AdamW decay, w -= lr * WD * w; with "
+                        "decoupled AdamW decay, w -= lr * WD * w (the same "
+                        "with --optimizer muon); with "
                         "--optimizer lamb: u += WD * w before the trust ratio")
-    p.add_argument("--optimizer", choices=("sgd", "adam", "lamb"),
+    p.add_argument("--optimizer", choices=("sgd", "adam", "lamb", "muon"),
                    default="sgd",
                    help="sgd: the fused SGD pass (--momentum, --lars_eta). "
                         "adam: fused Adam / AdamW. lamb: LAMB (You et al. "
@@ -256,7 +269,12 @@ def build_train_parser() -> argparse.ArgumentParser:
                         "|w| / |update|, the norms reduced on the device in a "
                         "fixed order; biases get plain Adam. Both keep two "
                         "fp32 moment buffers (checkpointed as flat_adam_m / "
-                        "flat_adam_v); not with --momentum or --lars_eta")
+                        "flat_adam_v); not with --momentum or --lars_eta. "
+                        "muon: Nesterov momentum (--momentum) whose update of "
+                        "every weight tensor is orthogonalised by five "
+                        "Newton-Schulz iterations on the matrix cores, "
+                        "decoupled --weight_decay; biases get plain momentum; "
+                        "not with --lars_eta or --adam_*")
     p.add_argument("--adam_beta1", type=_decay, default=None, metavar="B1",
                    help="first-moment decay in [0, 1) (default 0.9)")
     p.add_argument("--adam_beta2", type=_decay, default=None, metavar="B2",

@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
-"""Cost of --optimizer adam|lamb.  For every batch size it times the graphed
-LeNet training step (synthetic data, one GPU) in four variants:
+"""Cost of --optimizer adam|lamb|muon.  For every batch size it times the
+graphed LeNet training step (synthetic data, one GPU) in five variants:
 
   momentum  --momentum 0.9 (sgd_step_kernel with momentum), the baseline
   sgd       no optimizer flag, the default path
   adam      --optimizer adam --weight_decay 1e-2: adam_step_kernel
   lamb      --optimizer lamb --weight_decay 1e-2: lamb_moments_kernel +
             lamb_apply_kernel
+  muon      --optimizer muon --momentum 0.95 --weight_decay 1e-2: the kernel
+            sequence of csrc/muon.hip
 
 Every variant is warmed up (the capture happens there), then timed over
 `--steps` steps between two device events with one synchronise at the end.
@@ -28,7 +30,9 @@ from tools.clipbench import spread, timed  # noqa: E402
 
 VARIANTS = {"momentum": ["--momentum", "0.9"], "sgd": [],
             "adam": ["--optimizer", "adam", "--weight_decay", "1e-2"],
-            "lamb": ["--optimizer", "lamb", "--weight_decay", "1e-2"]}
+            "lamb": ["--optimizer", "lamb", "--weight_decay", "1e-2"],
+            "muon": ["--optimizer", "muon", "--momentum", "0.95",
+                     "--weight_decay", "1e-2"]}
 
 
 def make_step(batch, extra, seed, train_dir):
@@ -84,7 +88,7 @@ def main():
                 ms[k].append(round(1e3 * timed(fn, args.steps) / args.steps,
                                    5))
         entry = {k: dict(spread(v), runs=v) for k, v in ms.items()}
-        for a in ("adam", "lamb"):
+        for a in ("adam", "lamb", "muon"):
             if a in ms:
                 entry[f"{a}-momentum_us"] = spread(
                     [round(1e3 * (p - q), 3)
