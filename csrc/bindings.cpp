@@ -1284,6 +1284,69 @@ void grad_norm(torch::Tensor grad, std::vector<int64_t> offsets,
                    clipped_steps.data_ptr<long>(), part, ticket, s);
 }
 
+// Top-k sparsification with error feedback of the flat fp32 bucket, on the
+// device (topk.hip): resid += grad, the ks[t] largest magnitudes of tensor t
+// leave resid for payload (int32 [2][K]: indices, value bits) and, with
+// dense, stay in grad; grad is zero elsewhere (everywhere without dense).
+void topk_compress(torch::Tensor grad, torch::Tensor resid,
+                   std::vector<int64_t> offsets, std::vector<int64_t> numels,
+                   std::vector<int64_t> ks, torch::Tensor payload,
+                   bool dense) {
+  CHECK_CUDA(grad); CHECK_F32(grad); CHECK_CONTIG(grad);
+  CHECK_CUDA(resid); CHECK_F32(resid); CHECK_CONTIG(resid);
+  CHECK_CUDA(payload); CHECK_CONTIG(payload);
+  const int64_t n = grad.numel();
+  TORCH_CHECK(n >= 1 && n < (int64_t(1) << 31),
+              "topk_compress: 1 <= n < 2^31 elements");
+  TORCH_CHECK(resid.numel() == n,
+              "topk_compress: resid and grad hold the same number of values");
+  GradNormSegs segs = tiling_segs("topk_compress", offsets, numels, n);
+  TORCH_CHECK(ks.size() == offsets.size(),
+              "topk_compress: one k per segment");
+  TopkSegs tk{};
+  int64_t K = 0;
+  for (int i = 0; i < segs.n; ++i) {
+    TORCH_CHECK(ks[i] >= (numels[i] > 0 ? 1 : 0) && ks[i] <= numels[i],
+                "topk_compress: 1 <= k <= numel for every non-empty segment");
+    tk.k[i] = (int)ks[i];
+    tk.base[i] = (int)K;
+    K += ks[i];
+  }
+  TORCH_CHECK(payload.scalar_type() == at::kInt && payload.numel() == 2 * K,
+              "topk_compress: payload is int32 [2][sum of ks]");
+  TORCH_CHECK(resid.get_device() == grad.get_device() &&
+              payload.get_device() == grad.get_device(),
+              "topk_compress: resid and payload live on grad's device");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(grad.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(resid.data_ptr()) % 16 == 0,
+              "topk_compress: grad and resid must be 16-byte aligned");
+  auto s = cur_stream();
+  static auto* ws = new WorkspaceSlots(64);
+  int* w = device_workspace(
+      *ws, grad, TOPK_WS_INTS, at::kInt, s, "topk_compress",
+      "topk_compress: first call on a device allocates its workspace and "
+      "must run outside graph capture").data_ptr<int>();
+  launch_topk_compress(grad.data_ptr<float>(), resid.data_ptr<float>(), n,
+                       segs, tk, (int)K, payload.data_ptr<int>(),
+                       dense ? 1 : 0, w, s);
+}
+
+// grad[index] += value for one rank's payload (int32 [2][K]); assign: grad is
+// zero and takes 0 + value.  One launch per rank, in rank order.
+void topk_scatter(torch::Tensor payload, torch::Tensor grad, bool assign) {
+  CHECK_CUDA(grad); CHECK_F32(grad); CHECK_CONTIG(grad);
+  CHECK_CUDA(payload); CHECK_CONTIG(payload);
+  TORCH_CHECK(payload.scalar_type() == at::kInt && payload.numel() % 2 == 0,
+              "topk_scatter: payload is int32 [2][K]");
+  TORCH_CHECK(payload.get_device() == grad.get_device(),
+              "topk_scatter: payload lives on grad's device");
+  TORCH_CHECK(grad.numel() < (int64_t(1) << 31),
+              "topk_scatter: n < 2^31 elements");
+  launch_topk_scatter(payload.data_ptr<int>(), (int)(payload.numel() / 2),
+                      grad.data_ptr<float>(), grad.numel(), assign ? 1 : 0,
+                      cur_stream());
+}
+
 // LARS trust ratios of (master, grad) per tensor, on the device (lars.hip):
 // lars_tab [2 * GRAD_NORM_MAX_SEGS] and lars_stats [3 * segments] are stored;
 // clip > 0 also stores clip_stats / bumps clipped_steps exactly as grad_norm
@@ -2091,6 +2154,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           return std::make_tuple(blocks, chain);
         }, "(blocks, chain) of grad_norm on n elements: the grid, and the "
         "longest run of fp32 additions any element passes through");
+  m.def("topk_compress", &topk_compress,
+        "resid += grad; per segment the ks[t] largest magnitudes (ties by "
+        "index) move from resid into payload [2][K] in ascending index "
+        "order; grad keeps them (dense) or is zeroed; integer atomics only",
+        py::arg("grad"), py::arg("resid"), py::arg("offsets"),
+        py::arg("numels"), py::arg("ks"), py::arg("payload"),
+        py::arg("dense") = true);
+  m.def("topk_scatter", &topk_scatter,
+        "grad[index] += value for the pairs of one payload [2][K]; assign: "
+        "grad is zero, no load",
+        py::arg("payload"), py::arg("grad"), py::arg("assign") = false);
   m.def("lars_norm", &lars_norm,
         "LARS: lars_tab[2t] = ratio_t * coef, lars_tab[2t + 1] = ratio_t * wd "
         "/ grad_scale, lars_stats[3t..] = (|w_t|, coef * grad_scale * |g_t|, "

@@ -271,6 +271,31 @@ void launch_muon_update(float* master, float* grad, const float* mom,
                         const float* lr_scale_dev, const long* offset_dev,
                         int zero_grad, float* ema, float ema_decay,
                         hipStream_t);
+// topk.hip — top-k sparsification of the flat fp32 gradient with error
+// feedback (--grad_topk).  a = resid + grad; per segment t of segs the k[t]
+// elements first under "larger bits(a) & 0x7fffffff, then smaller index" are
+// selected.  STORED: payload[base[t] + j] = index and payload[K + base[t] +
+// j] = bits(a) of segment t's j-th selected element in ascending index order
+// (K = sum of k, base = its exclusive prefix sums); resid = 0 where selected,
+// a elsewhere; grad = a where selected and dense != 0, 0 elsewhere.  grad and
+// resid 16 B aligned, n < 2^31.  ws: a persistent zero-initialised workspace
+// of TOPK_WS_INTS ints (histograms, the per-segment table, per-block counts,
+// a self-resetting ticket; launches on one device must not overlap).  Five
+// launches, integer atomics only: a pure function of (grad, resid, segs, k).
+#define TOPK_BINS 2048
+#define TOPK_WS_INTS (GRAD_NORM_MAX_SEGS * TOPK_BINS + 4 * GRAD_NORM_MAX_SEGS + \
+                      2 * GRAD_NORM_MAX_SEGS * GRAD_NORM_MAX_BLOCKS + 1)
+struct TopkSegs {
+  int k[GRAD_NORM_MAX_SEGS];
+  int base[GRAD_NORM_MAX_SEGS];
+};
+void launch_topk_compress(float* grad, float* resid, long n, GradNormSegs segs,
+                          TopkSegs ks, int K, int* payload, int dense, int* ws,
+                          hipStream_t);
+// grad[index] += value for the K pairs of one payload (indices unique);
+// assign: grad is known to be zero, grad[index] = 0 + value without the load
+void launch_topk_scatter(const int* payload, int K, float* grad, long n,
+                         int assign, hipStream_t);
 // ema != nullptr (both launchers): the same pass also moves the fp32 moving
 // average towards the new master, e -= (1 - d_k)*(e - w) with
 // d_k = min(ema_decay, (1 + k)/(10 + k)), k = offset + 1 (a second

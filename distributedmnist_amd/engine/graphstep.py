@@ -114,6 +114,14 @@ class GraphedStep:
             getattr(t, "flat_adam_m", None), getattr(t, "flat_adam_v", None),
             getattr(t, "lamb_tab", None), t.lars_stats if lamb else None)
             if b is not None]
+        # --grad_topk: the warmup's gradients move the residual too.  With
+        # more than one rank the gather and the scatters run eagerly between
+        # the captured gradients and the tail (the single split scope)
+        self._topk = getattr(t, "topk_ks", None) is not None
+        if self._topk:
+            adam0.append((t.flat_topk_residual, t.flat_topk_residual.clone()))
+            assert split or not t.engine.distributed, \
+                "--grad_topk at world > 1 needs the split capture scope"
         t.model.set_step_dev(self.step_dev)
 
         if self.split and self._fused is not None:
@@ -125,6 +133,9 @@ class GraphedStep:
             # step's in-body fc all-reduce would fire before the mask, so
             # fall back to the post-body whole-bucket reduce in _body
             # (only reachable via --hip_graph full at world > 1)
+            self._fused.overlap_allreduce = False
+        if self._topk and self._fused is not None:
+            # as in eager mode: the sparse exchange replaces the all-reduce
             self._fused.overlap_allreduce = False
 
         self._prime(t.step)
@@ -159,6 +170,7 @@ class GraphedStep:
         # falls back to the single compute graph.
         import os as _os
         self.two_graph = (self.split and self._fused is not None
+                          and not self._topk  # whole-bucket selection
                           and _os.environ.get("DMNIST_SPLIT2", "1") != "0")
         fp = t.fp
         fc0 = fp.offsets[fp.names.index("fc1_w")]
@@ -306,6 +318,14 @@ class GraphedStep:
             # grads complete, reduce not yet issued: per-rank mask here
             self._ext.grad_mask(fp.flat_grad, self.dc_prob, t.flags.seed,
                                 0, t.rank, base=0, step_dev=self.step_dev)
+        if self._topk:
+            # every argument is device-resident or a capture constant; the
+            # first call (warmup) runs outside capture and allocates the
+            # kernels' workspace
+            self._ext.topk_compress(fp.flat_grad, t.flat_topk_residual,
+                                    fp.offsets, fp.numels, t.topk_ks,
+                                    t.engine.topk_payload,
+                                    dense=not t.engine.distributed)
         self.static_loss = loss.detach()
         self.static_acc = acc.detach()
         return fused_reduced
@@ -431,7 +451,9 @@ class GraphedStep:
             self._tail()
         elif self.split:
             t = self.t
-            if t.world > 1 and dist.is_initialized():
+            if self._topk:
+                t.engine.sparse_exchange()
+            elif t.world > 1 and dist.is_initialized():
                 t.engine.wire_allreduce(t.fp.flat_grad)
             self._tail()
         self.t.step += 1

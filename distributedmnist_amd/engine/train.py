@@ -30,6 +30,7 @@ import torch.distributed as dist
 from .. import _C
 from ..data import DeviceDataSet, SyntheticDataSet
 from ..models import build_model
+from ..ops import cpu_ref
 from ..ops import functional as Fx
 from ..parallel import FlatParams, StepTimer, SyncEngine
 from .supervisor import Supervisor
@@ -161,8 +162,47 @@ class Trainer:
         self.evaluator = None
         self.test_acc = 0.0      # most recent held-out precision
         self.eval_history = []   # (step, precision, loss) per evaluation
+        # --grad_topk RATIO: top-k sparsification with error feedback
+        # (ops.functional.topk_compress).  After the local gradient and the
+        # pre-aggregation drop-connect mask, the gradient is added to this
+        # rank's fp32 residual, the k_t largest magnitudes of every tensor
+        # leave it as (index, value) pairs and the rest stays for later
+        # steps.  The engine gathers the pairs and every rank adds them into
+        # the bucket in rank order, so all hold the same bits; everything
+        # after that (1/contributors, clipping, the optimizers) is unchanged.
+        self.topk = float(getattr(flags, "grad_topk", 0.0) or 0.0)
+        if not 0.0 <= self.topk <= 1.0:
+            raise ValueError("--grad_topk must be 0 (off) or lie in (0, 1], "
+                             f"got {self.topk}")
+        self.topk_ks = self.flat_topk_residual = None
+        if self.topk > 0:
+            def conflict(what, why):
+                raise ValueError(f"--grad_topk cannot be combined with "
+                                 f"{what}: {why}")
+            if mode == "interval":
+                conflict("--interval_method",
+                         "the interval accumulator is dense")
+            if mode == "k_of_n":
+                conflict("--num_replicas_to_aggregate below the world size",
+                         "a dropped payload would lose its residual")
+            if (flags.straggler_timeout_ms or 0) > 0:
+                conflict("--straggler_timeout_ms > 0",
+                         "a dropped payload would lose its residual")
+            if getattr(flags, "grad_dtype", "fp32") == "bf16":
+                conflict("--grad_dtype bf16",
+                         "the payload is index + fp32 value pairs")
+            if world > 1 and getattr(flags, "hip_graph", "auto") == "full":
+                conflict("--hip_graph full at world > 1",
+                         "the exchange runs between the captured gradients "
+                         "and the update")
+            if len(self.fp.names) > 16:
+                raise ValueError("--grad_topk supports at most 16 parameter "
+                                 "tensors")
+            self.topk_ks = cpu_ref.topk_ks(self.fp.numels, self.topk)
+            self.flat_topk_residual = torch.zeros_like(self.fp.flat_grad)
         self.engine = SyncEngine(
             self.fp.flat_grad, mode=mode,
+            topk_pairs=sum(self.topk_ks) if self.topk_ks else 0,
             replicas_to_aggregate=flags.num_replicas_to_aggregate,
             interval_ms=flags.interval_ms,
             straggler_timeout_ms=(flags.straggler_timeout_ms or None),
@@ -419,8 +459,11 @@ class Trainer:
             # including the RCCL all-reduce.
             force_full = (getattr(flags, "hip_graph", "auto") == "full"
                           or bool(os.environ.get("DMNIST_FORCE_GRAPH")))
+            # --grad_topk keeps the split scope whatever the diagnostic env
+            # says (--hip_graph full is refused at start-up): its exchange
+            # runs between the captured gradients and the tail
             split = (self.world > 1 and dist.is_initialized()
-                     and not force_full)
+                     and (not force_full or self.topk_ks is not None))
             self._graph = try_graph(self, batch_shape, split=split,
                                     dataset=self._resident_ds)
         if self.world > 1 and dist.is_initialized():
@@ -555,6 +598,13 @@ class Trainer:
         if self._dc_pre:
             Fx.grad_mask(self.fp.flat_grad, flags.drop_connect_probability,
                          flags.seed, self.step, self.rank)
+        if self.topk_ks is not None:
+            # the bucket becomes the selected values (one rank) or zeros for
+            # the engine's rank-ordered scatter of every rank's pairs
+            Fx.topk_compress(self.fp.flat_grad, self.flat_topk_residual,
+                             self.fp.offsets, self.fp.numels, self.topk_ks,
+                             payload=self.engine.topk_payload,
+                             dense=not self.engine.distributed)
         compute_time = self.timer.stop() if timed else 0.0
         applied, grad, contributors = self.engine.reduce(self.step, compute_time)
         if applied:
@@ -661,6 +711,29 @@ class Trainer:
         return {name: tuple(s[3 * i:3 * i + 3])
                 for i, name in enumerate(self.fp.names)}
 
+    def topk_stats(self):
+        """{tensor name: (k, threshold_magnitude, kept_fraction_of_l1)} of
+        the most recent step under --grad_topk, from this rank's payload and
+        residual: the pairs sent, the smallest magnitude among them and the
+        share of the step's sum |residual + gradient| they carry.  Reduced on
+        the device, then one read: for tools and tests, not for the step
+        loop."""
+        if self.topk_ks is None:
+            raise RuntimeError("topk_stats() needs --grad_topk > 0")
+        mags = self.engine.topk_payload[1].view(torch.float32).abs()
+        rows, base = [], 0
+        for o, m, k in zip(self.fp.offsets, self.fp.numels, self.topk_ks):
+            sent = mags[base:base + k]
+            kept = sent.double().sum()
+            left = self.flat_topk_residual[o:o + m].abs().double().sum()
+            rows.append(torch.stack([
+                sent.min().double() if k else kept, kept, kept + left]))
+            base += k
+        s = torch.stack(rows).cpu().tolist()
+        return {name: (k, thr, kept / total if total > 0 else 1.0)
+                for name, k, (thr, kept, total)
+                in zip(self.fp.names, self.topk_ks, s)}
+
     # -- in-training evaluation (--eval_every_steps) ----------------------
     def attach_eval_dataset(self, ds):
         """Build the DeviceEvaluator on `ds`, this rank's DeviceDataSet
@@ -738,6 +811,18 @@ class Trainer:
                         "--moving_average_decay): starting the average from "
                         "the restored weights", step0)
                     self.flat_ema.copy_(self.fp.flat_master)
+            if self.flat_topk_residual is not None:
+                # the checkpoint holds the chief's residual: resuming at
+                # world 1 is exact, every other rank's memory is gone
+                saved = payload.get("flat_topk_residual")
+                if self.is_chief and saved is not None:
+                    self.flat_topk_residual.copy_(saved.to(self.device))
+                else:
+                    log.warning(
+                        "checkpoint at step %d carries no top-k residual for "
+                        "rank %d (only the chief's is saved, and only with "
+                        "--grad_topk): starting it at zero", step0, self.rank)
+                    self.flat_topk_residual.zero_()
             self.step = step0
             if self.is_chief:
                 log.info("Restored checkpoint at step %d", step0)
@@ -843,6 +928,12 @@ class Trainer:
                 log.info("Gradient clipping (--clip_grad_norm %g): %d of %d "
                          "updates clipped", self.clip,
                          int(self.clipped_steps.item()), self.clip_updates)
+            if self.topk_ks is not None:
+                pairs = sum(self.topk_ks)
+                log.info("Top-k sparsification (--grad_topk %g): %d pairs = "
+                         "%d bytes sent per step per rank, dense bucket %d "
+                         "bytes", self.topk, pairs, 8 * pairs,
+                         4 * self.fp.flat_grad.numel())
             sv.save(self.step, self.checkpoint_payload())
         if self.world > 1 and dist.is_initialized():
             dist.barrier()
@@ -859,6 +950,9 @@ class Trainer:
                             if self.flat_adam_m is not None else None),
             "flat_adam_v": (self.flat_adam_v.detach().cpu().clone()
                             if self.flat_adam_v is not None else None),
+            "flat_topk_residual": (
+                self.flat_topk_residual.detach().cpu().clone()
+                if self.flat_topk_residual is not None else None),
             "model_state": {k: v.cpu() for k, v in
                             self.fp.state_dict_params().items()},
             "model": self.flags.model,

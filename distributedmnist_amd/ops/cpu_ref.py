@@ -303,6 +303,63 @@ def grad_norm(flat, offsets, numels, grad_scale: float, clip: float):
                         device=flat.device)
 
 
+def topk_ks(numels, ratio: float):
+    """--grad_topk RATIO: pairs sent per tensor, min(n, max(1, ceil(RATIO *
+    n))); an empty tensor sends none."""
+    if not 0.0 < ratio <= 1.0:  # also refuses nan
+        raise ValueError(f"topk_ks: ratio must lie in (0, 1], got {ratio}")
+    return [min(int(n), max(1, math.ceil(ratio * int(n)))) for n in numels]
+
+
+def topk_compress(g, r, offsets, numels, ks):
+    """Top-k sparsification with error feedback, the contract of
+    csrc/topk.hip.  a = r + g (one fp32 add per element); per segment the
+    ks[t] elements first under "larger bits(a) & 0x7fffffff, then smaller
+    index" are selected.  Returns (payload, dense): payload int32 [2][K], the
+    selected global indices in ascending order per segment (segment t in the
+    slots from sum(ks[:t])), then the bits of their a; dense = a where
+    selected, 0 elsewhere.  r is updated in place: 0 where selected, a
+    elsewhere.  Exact: integer compares only."""
+    if g.dtype != torch.float32 or g.dim() != 1 or r.shape != g.shape:
+        raise ValueError("topk_compress: g and r are 1-D fp32 of one length")
+    if not len(offsets) == len(numels) == len(ks):
+        raise ValueError("topk_compress: one length and one k per offset")
+    a = r + g
+    abits = a.view(torch.int32)
+    keys = abits & 0x7FFFFFFF
+    K = int(sum(ks))
+    payload = torch.zeros(2, K, dtype=torch.int32, device=g.device)
+    dense = torch.zeros_like(a)
+    base = 0
+    for o, m, k in zip(offsets, numels, ks):
+        if not (0 <= k <= m and (k >= 1 or m == 0)):
+            raise ValueError(f"topk_compress: k = {k} for {m} elements")
+        if k == 0:
+            continue
+        # stable: equal keys keep their index order
+        order = torch.sort(keys[o:o + m], descending=True, stable=True)[1]
+        idx = torch.sort(order[:k])[0] + o
+        payload[0, base:base + k] = idx.to(torch.int32)
+        payload[1, base:base + k] = abits[idx]
+        dense[idx] = a[idx]
+        a[idx] = 0.0
+        base += k
+    r.copy_(a)
+    return payload, dense
+
+
+def topk_scatter(payloads, n: int):
+    """The dense fp32 bucket [n] of the ranks' payloads (int32 [W][2][K]):
+    zeros, then g[index] += value rank by rank in rank order (indices are
+    unique within one rank), so every rank that runs this holds the same
+    bits."""
+    payloads = payloads.reshape(-1, 2, payloads.shape[-1])
+    g = torch.zeros(n, dtype=torch.float32, device=payloads.device)
+    for p in payloads:
+        g[p[0].long()] += p[1].view(torch.float32)
+    return g
+
+
 def lars_norm(master, flat, offsets, numels, adapt_mask: int,
               grad_scale: float, eta: float, wd: float, clip: float = 0.0):
     """LARS trust ratios (You, Gitman, Ginsburg 2017) of the flat fp32

@@ -330,6 +330,55 @@ def grad_norm(flat: torch.Tensor, offsets, numels, grad_scale: float,
     return stats
 
 
+def topk_compress(g: torch.Tensor, r: torch.Tensor, offsets, numels, ks,
+                  payload=None, dense: bool = True):
+    """Top-k sparsification with error feedback of the flat fp32 bucket `g`
+    against the residual `r` (ops/cpu_ref.py::topk_compress is the contract):
+    r += g, the ks[t] largest magnitudes of every (offset, numel) segment
+    leave r for `payload` (int32 [2][sum(ks)], written in place when given).
+    `g` is rewritten IN PLACE: the selected values and zeros elsewhere, or
+    all zeros with dense=False (the multi-rank exchange scatters every rank's
+    pairs into it).  Returns (payload, g).  On the GPU the five launches of
+    csrc/topk.hip: device-resident, hipGraph-capturable (after a first call
+    outside capture), integer atomics only, so equal inputs give equal
+    bits."""
+    offsets, numels = [int(o) for o in offsets], [int(m) for m in numels]
+    ks = [int(k) for k in ks]
+    if payload is None:
+        payload = torch.empty(2, sum(ks), dtype=torch.int32, device=g.device)
+    if g.is_cuda:
+        _C.ext().topk_compress(g, r, offsets, numels, ks, payload,
+                               dense=bool(dense))
+    else:
+        p, d = cpu_ref.topk_compress(g, r, offsets, numels, ks)
+        payload.copy_(p)
+        if dense:
+            g.copy_(d)
+        else:
+            g.zero_()
+    return payload, g
+
+
+def topk_scatter(payloads: torch.Tensor, n: int, out=None):
+    """Dense fp32 bucket [n] of the ranks' payloads (int32 [W][2][K]): zeros,
+    then every rank's pairs added in rank order (ops/cpu_ref.py::
+    topk_scatter).  `out`, when given, is the bucket to fill and must hold
+    zeros.  On the GPU one topk_scatter_kernel launch per rank on the current
+    stream, which fixes the order of the sums."""
+    payloads = payloads.reshape(-1, 2, payloads.shape[-1])
+    if out is None:
+        out = torch.zeros(n, dtype=torch.float32, device=payloads.device)
+    if out.numel() != n:
+        raise ValueError(f"topk_scatter: out holds {out.numel()} values, "
+                         f"not {n}")
+    if payloads.is_cuda:
+        for w in range(payloads.shape[0]):
+            _C.ext().topk_scatter(payloads[w], out, assign=(w == 0))
+    else:
+        out.copy_(cpu_ref.topk_scatter(payloads, n))
+    return out
+
+
 def lars_norm(master: torch.Tensor, flat: torch.Tensor, offsets, numels,
               adapt_mask: int, grad_scale: float, eta: float, wd: float,
               clip: float = 0.0, lars_tab=None, lars_stats=None,

@@ -48,9 +48,26 @@ class SyncEngine:
                  straggler_timeout_ms: float | None = None,
                  group=None, rank: int = 0, world_size: int = 1,
                  cdf_log_every: int = 50, cdf_start_tracking: int = 20,
-                 wire_dtype: torch.dtype | None = None):
+                 wire_dtype: torch.dtype | None = None, topk_pairs: int = 0):
         if mode not in MODES:
             raise ValueError(f"mode {mode!r} not in {MODES}")
+        # --grad_topk: the sparse exchange replaces the dense all-reduce.
+        # topk_payload is this rank's [2][K] (indices, value bits) of the
+        # step, written by ops.functional.topk_compress; topk_gather holds
+        # every rank's after the all-gather.  K is a constant of the run.
+        self.topk_payload = self.topk_gather = None
+        self._gather_list = False
+        if topk_pairs > 0:
+            if (mode not in ("full_sync", "cdf") or wire_dtype is not None
+                    or straggler_timeout_ms):
+                raise ValueError("the sparse exchange serves full_sync / cdf "
+                                 "with an fp32 wire and no straggler timeout")
+            self.topk_payload = torch.zeros(2, topk_pairs, dtype=torch.int32,
+                                            device=flat_grad.device)
+            if world_size > 1:
+                self.topk_gather = torch.zeros(
+                    world_size, 2, topk_pairs, dtype=torch.int32,
+                    device=flat_grad.device)
         self.mode = mode
         self.flat_grad = flat_grad
         self.group = group
@@ -113,6 +130,31 @@ class SyncEngine:
             dist.all_reduce(w, op=dist.ReduceOp.SUM, group=self.group)
             tensor.copy_(w)
 
+    def sparse_exchange(self):
+        """--grad_topk at world > 1: ONE all-gather of the [2][K] payloads,
+        then every rank's pairs added into the bucket in rank order (the
+        compression left it zero).  All ranks perform the same additions in
+        the same order, so all hold the same bits.  Also the eager half of
+        the graphed split step.  No collective at world 1: the compression
+        already wrote the dense bucket in place."""
+        if not self.distributed:
+            return
+        from ..ops import functional as Fx
+        if not self._gather_list:
+            try:
+                dist.all_gather_into_tensor(self.topk_gather,
+                                            self.topk_payload,
+                                            group=self.group)
+            except (RuntimeError, NotImplementedError):
+                # the backend has no tensor form for this device: refused
+                # before anything is sent, the same on every rank
+                self._gather_list = True
+        if self._gather_list:
+            dist.all_gather(list(self.topk_gather.unbind(0)),
+                            self.topk_payload, group=self.group)
+        Fx.topk_scatter(self.topk_gather, self.flat_grad.numel(),
+                        out=self.flat_grad)
+
     # ------------------------------------------------------------------
     def step_begin(self, step: int):
         self._t_start = time.time()
@@ -161,7 +203,9 @@ class SyncEngine:
         # hot path: pure synchronous all-reduce, no staging copies, no
         # host round-trips — the collective IS the barrier
         if self.mode in ("full_sync", "cdf") and self.timeout_s is None:
-            if self.distributed:
+            if self.topk_payload is not None:
+                self.sparse_exchange()
+            elif self.distributed:
                 if self.wire_dtype is None:
                     dist.all_reduce(self.flat_grad, op=dist.ReduceOp.SUM,
                                     group=self.group)

@@ -50,6 +50,18 @@ def _lars_eta(text: str) -> float:
     return v
 
 
+def _grad_topk(text: str) -> float:
+    """--grad_topk: 0 (off) or a ratio in (0, 1]."""
+    try:
+        v = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a number: {text!r}")
+    if not 0.0 <= v <= 1.0:  # also refuses nan
+        raise argparse.ArgumentTypeError(
+            f"must be 0 (off) or lie in (0, 1], got {text}")
+    return v
+
+
 def _adam_eps(text: str) -> float:
     """--adam_eps: finite and > 0."""
     try:
@@ -95,6 +107,19 @@ class _TrainParser(argparse.ArgumentParser):
             if ns.lars_eta > 0:
                 self.error("argument --lars_eta: not with --optimizer "
                            f"{ns.optimizer} (lamb is the Adam-based LARS)")
+        if ns.grad_topk > 0:
+            # the sparse exchange replaces the dense synchronous all-reduce
+            # only (the checks that need the world size: Trainer)
+            for bad, what in (
+                    (ns.interval_method, "--interval_method (the interval "
+                     "accumulator is dense)"),
+                    ((ns.straggler_timeout_ms or 0) > 0,
+                     "--straggler_timeout_ms > 0 (a dropped payload would "
+                     "lose its residual)"),
+                    (ns.grad_dtype == "bf16", "--grad_dtype bf16 (the "
+                     "payload is index + fp32 value pairs)")):
+                if bad:
+                    self.error(f"argument --grad_topk: not with {what}")
         # the defaults, once the "was it given" check is done
         for name, default in (("adam_beta1", 0.9), ("adam_beta2", 0.999),
                               ("adam_eps", 1e-8)):
@@ -184,6 +209,21 @@ def build_train_parser() -> argparse.ArgumentParser:
     p.add_argument("--grad_dtype", default="fp32", choices=["fp32", "bf16"],
                    help="all-reduce wire dtype: bf16 halves the xGMI payload "
                         "(6.65->3.33 MB); the fp32 master update is unchanged")
+    p.add_argument("--grad_topk", type=_grad_topk, default=0.0,
+                   metavar="RATIO",
+                   help="RATIO in (0, 1]: top-k gradient sparsification with "
+                        "error feedback (Aji & Heafield 2017, Stich et al. "
+                        "2018). Every rank adds its gradient to a local "
+                        "residual, sends the ceil(RATIO * n) largest "
+                        "magnitudes of every tensor as (index, value) pairs "
+                        "(one all-gather) and keeps the rest in the "
+                        "residual; the pairs are summed in rank order, so "
+                        "all ranks hold the same bits. Selected on the "
+                        "device by a radix select in a fixed order. Not "
+                        "with --interval_method, --num_replicas_to_aggregate "
+                        "below the world size, --straggler_timeout_ms, "
+                        "--grad_dtype bf16 or --hip_graph full at world > 1. "
+                        "0 = off")
     p.add_argument("--drop_connect_post", action="store_true",
                    help="legacy round-1 form: one shared mask on the "
                         "AGGREGATED gradient (default is the reference's "
