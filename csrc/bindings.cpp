@@ -1347,6 +1347,136 @@ void topk_scatter(torch::Tensor payload, torch::Tensor grad, bool assign) {
                       cur_stream());
 }
 
+// PowerSGD rank-R compression (lowrank.hip).  The four ops share one
+// description of the bucket: the compressed matrices (offsets, rows, cols;
+// ascending, disjoint, each passing lowrank_fits), the rank, and `pack`: the
+// rest of the bucket travels behind P in the wire buffer.
+struct LowrankCall {
+  LowrankDesc d;
+  int64_t p_floats, q_floats, wire_floats;
+};
+
+static LowrankCall lowrank_call(const char* who, int64_t n,
+                                const std::vector<int64_t>& offsets,
+                                const std::vector<int64_t>& rows,
+                                const std::vector<int64_t>& cols, int64_t R,
+                                bool pack) {
+  const size_t nt = offsets.size();
+  TORCH_CHECK(nt >= 1 && nt <= LOWRANK_MAX_TENSORS && rows.size() == nt &&
+              cols.size() == nt, who, ": 1 to ", LOWRANK_MAX_TENSORS,
+              " compressed tensors, one (rows, cols) per offset");
+  TORCH_CHECK(R >= 1 && R <= LOWRANK_MAX_RANK, who, ": 1 <= rank <= ",
+              LOWRANK_MAX_RANK);
+  TORCH_CHECK(n >= 1 && n < (int64_t(1) << 31), who, ": 1 <= n < 2^31");
+  LowrankCall c{};
+  LowrankDesc& d = c.d;
+  d.n = (int)nt;
+  d.R = (int)R;
+  int64_t at = 0, dense = 0;
+  for (size_t t = 0; t < nt; ++t) {
+    TORCH_CHECK(lowrank_fits(offsets[t], rows[t], cols[t]), who, ": tensor ",
+                t, " [", rows[t], "][", cols[t], "] at ", offsets[t],
+                " cannot be compressed (offset % 4, rows % 16, cols % 16, "
+                "64 <= rows <= 4096, 64 <= cols <= 512)");
+    TORCH_CHECK(offsets[t] >= at && offsets[t] + rows[t] * cols[t] <= n, who,
+                ": the tensors must be ascending, disjoint and inside the "
+                "bucket");
+    if (pack && offsets[t] > at) {
+      d.doff[d.nd] = at;
+      d.dlen[d.nd++] = offsets[t] - at;
+      dense += offsets[t] - at;
+    }
+    d.off[t] = offsets[t];
+    d.rows[t] = (int)rows[t];
+    d.cols[t] = (int)cols[t];
+    d.poff[t] = c.p_floats;
+    d.qoff[t] = c.q_floats;
+    c.p_floats += rows[t] * R;
+    c.q_floats += cols[t] * R;
+    at = offsets[t] + rows[t] * cols[t];
+  }
+  if (pack && n > at) {
+    d.doff[d.nd] = at;
+    d.dlen[d.nd++] = n - at;
+    dense += n - at;
+  }
+  int64_t w = c.p_floats;
+  for (int s = 0; s < d.nd; ++s) {
+    d.dwire[s] = w;
+    w += d.dlen[s];
+  }
+  c.wire_floats = c.p_floats + dense;
+  lowrank_blocks(&d);
+  return c;
+}
+
+static void lowrank_check(const char* who, const torch::Tensor& t,
+                          int64_t numel, const torch::Tensor& like) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat &&
+              t.is_contiguous() && t.numel() == numel &&
+              t.get_device() == like.get_device() &&
+              reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+              who, ": every buffer is contiguous fp32 on one GPU, 16-byte "
+              "aligned, and holds exactly ", numel, " values here (got ",
+              t.numel(), ")");
+}
+
+void lowrank_p(torch::Tensor grad, torch::Tensor resid, torch::Tensor q,
+               torch::Tensor wire, std::vector<int64_t> offsets,
+               std::vector<int64_t> rows, std::vector<int64_t> cols,
+               int64_t rank, bool pack) {
+  const int64_t n = grad.numel();
+  LowrankCall c = lowrank_call("lowrank_p", n, offsets, rows, cols, rank, pack);
+  lowrank_check("lowrank_p", grad, n, grad);
+  lowrank_check("lowrank_p", resid, n, grad);
+  lowrank_check("lowrank_p", q, c.q_floats, grad);
+  lowrank_check("lowrank_p", wire, c.wire_floats, grad);
+  launch_lowrank_p(grad.data_ptr<float>(), resid.data_ptr<float>(),
+                   q.data_ptr<float>(), wire.data_ptr<float>(), c.d,
+                   cur_stream());
+}
+
+// orthonormalise P in the front of wire (anything behind it is left alone),
+// then qr = M^T P: the two launches between the two sums over ranks
+void lowrank_q(torch::Tensor resid, torch::Tensor wire, torch::Tensor qr,
+               std::vector<int64_t> offsets, std::vector<int64_t> rows,
+               std::vector<int64_t> cols, int64_t rank) {
+  const int64_t n = resid.numel();
+  LowrankCall c = lowrank_call("lowrank_q", n, offsets, rows, cols, rank,
+                               false);
+  TORCH_CHECK(wire.numel() >= c.p_floats, "lowrank_q: wire holds ",
+              wire.numel(), " values, P needs ", c.p_floats);
+  lowrank_check("lowrank_q", resid, n, resid);
+  lowrank_check("lowrank_q", wire, wire.numel(), resid);
+  lowrank_check("lowrank_q", qr, c.q_floats, resid);
+  auto s = cur_stream();
+  static auto* ws = new WorkspaceSlots(64);
+  float* w = device_workspace(
+      *ws, resid, LOWRANK_WS_FLOATS, at::kFloat, s, "lowrank_q",
+      "lowrank_q: first call on a device allocates its workspace and must "
+      "run outside graph capture").data_ptr<float>();
+  launch_lowrank_orth(wire.data_ptr<float>(), c.d, s);
+  launch_lowrank_q(resid.data_ptr<float>(), wire.data_ptr<float>(),
+                   qr.data_ptr<float>(), w, c.d, s);
+}
+
+void lowrank_expand(torch::Tensor grad, torch::Tensor resid,
+                    torch::Tensor wire, torch::Tensor qr, torch::Tensor qsum,
+                    std::vector<int64_t> offsets, std::vector<int64_t> rows,
+                    std::vector<int64_t> cols, int64_t rank, bool pack) {
+  const int64_t n = grad.numel();
+  LowrankCall c = lowrank_call("lowrank_expand", n, offsets, rows, cols, rank,
+                               pack);
+  lowrank_check("lowrank_expand", grad, n, grad);
+  lowrank_check("lowrank_expand", resid, n, grad);
+  lowrank_check("lowrank_expand", wire, c.wire_floats, grad);
+  lowrank_check("lowrank_expand", qr, c.q_floats, grad);
+  lowrank_check("lowrank_expand", qsum, c.q_floats, grad);
+  launch_lowrank_expand(grad.data_ptr<float>(), resid.data_ptr<float>(),
+                        wire.data_ptr<float>(), qr.data_ptr<float>(),
+                        qsum.data_ptr<float>(), c.d, cur_stream());
+}
+
 // LARS trust ratios of (master, grad) per tensor, on the device (lars.hip):
 // lars_tab [2 * GRAD_NORM_MAX_SEGS] and lars_stats [3 * segments] are stored;
 // clip > 0 also stores clip_stats / bumps clipped_steps exactly as grad_norm
@@ -2165,6 +2295,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "grad[index] += value for the pairs of one payload [2][K]; assign: "
         "grad is zero, no load",
         py::arg("payload"), py::arg("grad"), py::arg("assign") = false);
+  m.def("lowrank_p", &lowrank_p,
+        "PowerSGD: resid = grad + resid (= M) on the compressed matrices, "
+        "P = M q into wire; pack: the rest of grad is copied behind P",
+        py::arg("grad"), py::arg("resid"), py::arg("q"), py::arg("wire"),
+        py::arg("offsets"), py::arg("rows"), py::arg("cols"), py::arg("rank"),
+        py::arg("pack") = false);
+  m.def("lowrank_q", &lowrank_q,
+        "PowerSGD: P in wire <- modified Gram-Schmidt of P (columns / (norm + "
+        "1e-8)), then qr = M^T P; fixed summation orders, no float atomics",
+        py::arg("resid"), py::arg("wire"), py::arg("qr"), py::arg("offsets"),
+        py::arg("rows"), py::arg("cols"), py::arg("rank"));
+  m.def("lowrank_expand", &lowrank_expand,
+        "PowerSGD: grad = P qsum^T, resid = M - P qr^T on the compressed "
+        "matrices (one product when qr is qsum); pack: the rest of grad is "
+        "taken back from behind P in wire",
+        py::arg("grad"), py::arg("resid"), py::arg("wire"), py::arg("qr"),
+        py::arg("qsum"), py::arg("offsets"), py::arg("rows"), py::arg("cols"),
+        py::arg("rank"), py::arg("pack") = false);
   m.def("lars_norm", &lars_norm,
         "LARS: lars_tab[2t] = ratio_t * coef, lars_tab[2t + 1] = ratio_t * wd "
         "/ grad_scale, lars_stats[3t..] = (|w_t|, coef * grad_scale * |g_t|, "

@@ -27,7 +27,8 @@ def main():
             ("gemm_tile.hip", "conv_slab.hip", "dw_tr.hip", "ops_misc.hip", "conv1_mfma.hip",
              "data_gather.hip", "elastic_gather.hip", "conv2_dw_slab.hip", "conv2_resident.hip",
              "eval_ops.hip",
-             "det_reduce.hip", "fc2_head.hip", "grad_norm.hip", "topk.hip", "lars.hip",
+             "det_reduce.hip", "fc2_head.hip", "grad_norm.hip", "topk.hip", "lowrank.hip",
+             "lars.hip",
              "adam.hip", "muon.hip", "bindings.cpp")]
     out = os.path.join(ROOT, "_dmnist_hip.so")
 

@@ -296,6 +296,57 @@ void launch_topk_compress(float* grad, float* resid, long n, GradNormSegs segs,
 // assign: grad is known to be zero, grad[index] = 0 + value without the load
 void launch_topk_scatter(const int* payload, int K, float* grad, long n,
                          int assign, hipStream_t);
+// lowrank.hip — PowerSGD rank-R compression of the flat fp32 gradient with
+// error feedback (--grad_lowrank).  Up to LOWRANK_MAX_TENSORS row-major
+// [rows][cols] matrices of the bucket that pass lowrank_fits, ascending and
+// disjoint.  wire: [P of tensor 0 | P of tensor 1 | .. | dense elements], P
+// [rows][R] packed, the dense gaps (nd of them, everything of the bucket
+// outside the matrices) only when they are packed for a multi-rank sum.  q,
+// qr, qsum: [Q of tensor 0 | ..], Q [cols][R] packed.
+//   lowrank_p:      resid = grad + resid on the matrices (= M), P = M Q into
+//                   wire, the dense gaps of grad copied behind P
+//   lowrank_orth:   P <- modified Gram-Schmidt of P, columns / (norm + 1e-8)
+//   lowrank_q:      qr = M^T P (ws: zero-initialised, LOWRANK_WS_FLOATS,
+//                   planes + self-resetting tickets; launches on one device
+//                   must not overlap)
+//   lowrank_expand: grad = P qsum^T and resid = M - P qr^T on the matrices
+//                   (qr == qsum: one product for both), the dense gaps of
+//                   grad taken back from wire
+// fp32 MFMA throughout, no float atomics, every summation order fixed by the
+// geometry: a pure function of the inputs.
+#define LOWRANK_MAX_TENSORS 4
+#define LOWRANK_MAX_RANK 16
+#define LOWRANK_MAX_ROWS 4096
+#define LOWRANK_MAX_COLS 512
+#define LOWRANK_Q_SLICE 128    // rows of M per block of lowrank_q
+#define LOWRANK_MAX_GROUPS (LOWRANK_MAX_COLS / 64)
+#define LOWRANK_PLANE_FLOATS \
+  ((LOWRANK_MAX_ROWS / LOWRANK_Q_SLICE) * LOWRANK_MAX_COLS * 16)
+#define LOWRANK_WS_FLOATS (LOWRANK_MAX_TENSORS * LOWRANK_PLANE_FLOATS + \
+                           LOWRANK_MAX_TENSORS * LOWRANK_MAX_GROUPS)
+struct LowrankDesc {
+  int n, R, nd;
+  long off[LOWRANK_MAX_TENSORS];   // bucket offset of the matrix
+  int rows[LOWRANK_MAX_TENSORS], cols[LOWRANK_MAX_TENSORS];
+  long poff[LOWRANK_MAX_TENSORS];  // of P in wire
+  long qoff[LOWRANK_MAX_TENSORS];  // of Q in q / qr / qsum
+  long doff[LOWRANK_MAX_TENSORS + 1];   // dense gap s: bucket offset,
+  long dlen[LOWRANK_MAX_TENSORS + 1];   //   length,
+  long dwire[LOWRANK_MAX_TENSORS + 1];  //   offset in wire
+  // first block of tensor t in the p / q / expand grids (lowrank_blocks)
+  int pblk[LOWRANK_MAX_TENSORS + 1], qblk[LOWRANK_MAX_TENSORS + 1],
+      xblk[LOWRANK_MAX_TENSORS + 1];
+};
+bool lowrank_fits(long off, long rows, long cols);
+void lowrank_blocks(LowrankDesc* d);
+void launch_lowrank_p(float* grad, float* resid, const float* q, float* wire,
+                      const LowrankDesc& d, hipStream_t);
+void launch_lowrank_orth(float* wire, const LowrankDesc& d, hipStream_t);
+void launch_lowrank_q(const float* resid, const float* wire, float* qr,
+                      float* ws, const LowrankDesc& d, hipStream_t);
+void launch_lowrank_expand(float* grad, float* resid, float* wire,
+                           const float* qr, const float* qsum,
+                           const LowrankDesc& d, hipStream_t);
 // ema != nullptr (both launchers): the same pass also moves the fp32 moving
 // average towards the new master, e -= (1 - d_k)*(e - w) with
 // d_k = min(ema_decay, (1 + k)/(10 + k)), k = offset + 1 (a second

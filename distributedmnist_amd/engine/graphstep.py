@@ -122,6 +122,15 @@ class GraphedStep:
             adam0.append((t.flat_topk_residual, t.flat_topk_residual.clone()))
             assert split or not t.engine.distributed, \
                 "--grad_topk at world > 1 needs the split capture scope"
+        # --grad_lowrank: as top-k.  With one rank all four kernels sit in
+        # the captured body; with more the two all-reduces and the kernels
+        # between and after them run eagerly before the tail
+        self._lowrank = getattr(t, "lowrank", None) is not None
+        if self._lowrank:
+            adam0 += [(b, b.clone()) for b in (t.flat_lowrank_residual,
+                                               t.flat_lowrank_q)]
+            assert split or not t.engine.distributed, \
+                "--grad_lowrank at world > 1 needs the split capture scope"
         t.model.set_step_dev(self.step_dev)
 
         if self.split and self._fused is not None:
@@ -134,7 +143,7 @@ class GraphedStep:
             # fall back to the post-body whole-bucket reduce in _body
             # (only reachable via --hip_graph full at world > 1)
             self._fused.overlap_allreduce = False
-        if self._topk and self._fused is not None:
+        if (self._topk or self._lowrank) and self._fused is not None:
             # as in eager mode: the sparse exchange replaces the all-reduce
             self._fused.overlap_allreduce = False
 
@@ -171,6 +180,7 @@ class GraphedStep:
         import os as _os
         self.two_graph = (self.split and self._fused is not None
                           and not self._topk  # whole-bucket selection
+                          and not self._lowrank
                           and _os.environ.get("DMNIST_SPLIT2", "1") != "0")
         fp = t.fp
         fc0 = fp.offsets[fp.names.index("fc1_w")]
@@ -326,6 +336,12 @@ class GraphedStep:
                                     fp.offsets, fp.numels, t.topk_ks,
                                     t.engine.topk_payload,
                                     dense=not t.engine.distributed)
+        if self._lowrank:
+            # as above; the workspace of lowrank_q is allocated by the warmup
+            from ..ops import functional as Fx
+            Fx.lowrank_p(fp.flat_grad, t.lowrank)
+            if not self.split:
+                t.engine.lowrank_exchange()
         self.static_loss = loss.detach()
         self.static_acc = acc.detach()
         return fused_reduced
@@ -453,6 +469,8 @@ class GraphedStep:
             t = self.t
             if self._topk:
                 t.engine.sparse_exchange()
+            elif self._lowrank:
+                t.engine.lowrank_exchange()
             elif t.world > 1 and dist.is_initialized():
                 t.engine.wire_allreduce(t.fp.flat_grad)
             self._tail()

@@ -200,9 +200,48 @@ class Trainer:
                                  "tensors")
             self.topk_ks = cpu_ref.topk_ks(self.fp.numels, self.topk)
             self.flat_topk_residual = torch.zeros_like(self.fp.flat_grad)
+        # --grad_lowrank R: PowerSGD compression with error feedback
+        # (ops.functional.LowrankState, ops/cpu_ref.py::lowrank_step).  At
+        # the same place as top-k: every weight matrix the plan accepts
+        # leaves as two thin factors, summed over the ranks in two small
+        # all-reduces; the bucket is then the SUM of the ranks' rank-R
+        # approximations, so everything after it is unchanged.
+        self.lowrank_rank = int(getattr(flags, "grad_lowrank", 0) or 0)
+        if not 0 <= self.lowrank_rank <= 16:
+            raise ValueError("--grad_lowrank must be 0 (off) or lie in "
+                             f"1..16, got {self.lowrank_rank}")
+        self.lowrank = None
+        self.flat_lowrank_residual = self.flat_lowrank_q = None
+        if self.lowrank_rank > 0:
+            def conflict(what, why):
+                raise ValueError(f"--grad_lowrank cannot be combined with "
+                                 f"{what}: {why}")
+            if self.topk > 0:
+                conflict("--grad_topk", "one compressor at a time")
+            if mode == "interval":
+                conflict("--interval_method",
+                         "the interval accumulator is dense")
+            if mode == "k_of_n":
+                conflict("--num_replicas_to_aggregate below the world size",
+                         "a dropped factor would lose its residual")
+            if (flags.straggler_timeout_ms or 0) > 0:
+                conflict("--straggler_timeout_ms > 0",
+                         "a dropped factor would lose its residual")
+            if getattr(flags, "grad_dtype", "fp32") == "bf16":
+                conflict("--grad_dtype bf16", "the factors stay fp32")
+            if world > 1 and getattr(flags, "hip_graph", "auto") == "full":
+                conflict("--hip_graph full at world > 1",
+                         "the exchange runs between the captured gradients "
+                         "and the update")
+            self.lowrank = Fx.LowrankState(
+                self.fp.shapes, self.fp.offsets, self.fp.flat_grad.numel(),
+                self.lowrank_rank, flags.seed, self.device, pack=world > 1)
+            self.flat_lowrank_residual = self.lowrank.resid
+            self.flat_lowrank_q = self.lowrank.q
         self.engine = SyncEngine(
             self.fp.flat_grad, mode=mode,
             topk_pairs=sum(self.topk_ks) if self.topk_ks else 0,
+            lowrank=self.lowrank,
             replicas_to_aggregate=flags.num_replicas_to_aggregate,
             interval_ms=flags.interval_ms,
             straggler_timeout_ms=(flags.straggler_timeout_ms or None),
@@ -463,7 +502,8 @@ class Trainer:
             # says (--hip_graph full is refused at start-up): its exchange
             # runs between the captured gradients and the tail
             split = (self.world > 1 and dist.is_initialized()
-                     and (not force_full or self.topk_ks is not None))
+                     and (not force_full or self.topk_ks is not None
+                          or self.lowrank is not None))
             self._graph = try_graph(self, batch_shape, split=split,
                                     dataset=self._resident_ds)
         if self.world > 1 and dist.is_initialized():
@@ -605,6 +645,9 @@ class Trainer:
                              self.fp.offsets, self.fp.numels, self.topk_ks,
                              payload=self.engine.topk_payload,
                              dense=not self.engine.distributed)
+        if self.lowrank is not None:
+            # M = G + E and P = M Q; the engine's reduce does the rest
+            Fx.lowrank_p(self.fp.flat_grad, self.lowrank)
         compute_time = self.timer.stop() if timed else 0.0
         applied, grad, contributors = self.engine.reduce(self.step, compute_time)
         if applied:
@@ -734,6 +777,24 @@ class Trainer:
                 for name, k, (thr, kept, total)
                 in zip(self.fp.names, self.topk_ks, s)}
 
+    def lowrank_stats(self):
+        """{tensor name: (rank, |E| / |M|)} of the compressed tensors after
+        the most recent step under --grad_lowrank: the share of this rank's
+        M = gradient + old residual that the factors missed.  |M| is taken as
+        sqrt(|E|^2 + |Q_r|^2): E is orthogonal to P^ Q_r^T and |P^ Q_r^T| =
+        |Q_r| for orthonormal P^.  Reduced on the device, then one read: for
+        tools and tests, not for the step loop."""
+        st = self.lowrank
+        if st is None:
+            raise RuntimeError("lowrank_stats() needs --grad_lowrank > 0")
+        sq = torch.stack([
+            torch.stack([st.views(st.resid, t).double().square().sum(),
+                         st.views(st.qr, t, st.cols).double().square().sum()])
+            for t in range(len(st.plan))]).cpu().tolist()
+        return {self.fp.names[p[0]]:
+                (st.R, (e / (e + q)) ** 0.5 if e + q > 0 else 0.0)
+                for p, (e, q) in zip(st.plan, sq)}
+
     # -- in-training evaluation (--eval_every_steps) ----------------------
     def attach_eval_dataset(self, ds):
         """Build the DeviceEvaluator on `ds`, this rank's DeviceDataSet
@@ -823,6 +884,24 @@ class Trainer:
                         "rank %d (only the chief's is saved, and only with "
                         "--grad_topk): starting it at zero", step0, self.rank)
                     self.flat_topk_residual.zero_()
+            if self.lowrank is not None:
+                # as the top-k residual: the chief's residual, exact at
+                # world 1; Q is the same on every rank
+                for key, buf, chief_only in (
+                        ("flat_lowrank_residual", self.flat_lowrank_residual,
+                         True),
+                        ("flat_lowrank_q", self.flat_lowrank_q, False)):
+                    saved = payload.get(key)
+                    if (saved is not None and saved.numel() == buf.numel()
+                            and (self.is_chief or not chief_only)):
+                        buf.copy_(saved.to(self.device))
+                    else:
+                        log.warning(
+                            "checkpoint at step %d carries no usable %s for "
+                            "rank %d (saved by the chief, and only with the "
+                            "same --grad_lowrank): starting from %s", step0,
+                            key, self.rank,
+                            "zero" if chief_only else "the seeded factors")
             self.step = step0
             if self.is_chief:
                 log.info("Restored checkpoint at step %d", step0)
@@ -934,6 +1013,13 @@ class Trainer:
                          "%d bytes sent per step per rank, dense bucket %d "
                          "bytes", self.topk, pairs, 8 * pairs,
                          4 * self.fp.flat_grad.numel())
+            if self.lowrank is not None:
+                st = self.lowrank
+                log.info("Low-rank compression (--grad_lowrank %d): %d "
+                         "tensors compressed, all-reduces of %d and %d floats "
+                         "per step, dense bucket %d floats", st.R,
+                         len(st.plan), st.p_floats + st.dense_floats,
+                         st.q_floats, self.fp.flat_grad.numel())
             sv.save(self.step, self.checkpoint_payload())
         if self.world > 1 and dist.is_initialized():
             dist.barrier()
@@ -953,6 +1039,11 @@ class Trainer:
             "flat_topk_residual": (
                 self.flat_topk_residual.detach().cpu().clone()
                 if self.flat_topk_residual is not None else None),
+            "flat_lowrank_residual": (
+                self.flat_lowrank_residual.detach().cpu().clone()
+                if self.flat_lowrank_residual is not None else None),
+            "flat_lowrank_q": (self.flat_lowrank_q.detach().cpu().clone()
+                               if self.flat_lowrank_q is not None else None),
             "model_state": {k: v.cpu() for k, v in
                             self.fp.state_dict_params().items()},
             "model": self.flags.model,

@@ -360,6 +360,93 @@ def topk_scatter(payloads, n: int):
     return g
 
 
+LOWRANK_MAX_TENSORS = 4
+
+
+def lowrank_plan(shapes, offsets, R: int):
+    """--grad_lowrank R: which tensors of the bucket are compressed.  Returns
+    [(index, offset, rows, cols)].  A tensor is viewed as [rows = numel /
+    shape[-1]][cols = shape[-1]] and compressed iff it has at least 2 dims,
+    rows % 16 == 0 == cols % 16, 64 <= rows <= 4096, 64 <= cols <= 512 and
+    its bucket offset is a multiple of 4; every other tensor is sent dense,
+    exactly, and has no residual."""
+    if not 1 <= int(R) <= 16:
+        raise ValueError(f"lowrank_plan: rank must lie in 1..16, got {R}")
+    plan = []
+    for i, (shape, off) in enumerate(zip(shapes, offsets)):
+        if len(shape) < 2:
+            continue
+        cols = int(shape[-1])
+        rows = int(math.prod(shape)) // max(cols, 1)
+        if (rows % 16 == 0 and cols % 16 == 0 and 64 <= rows <= 4096
+                and 64 <= cols <= 512 and int(off) % 4 == 0):
+            plan.append((i, int(off), rows, cols))
+    if len(plan) > LOWRANK_MAX_TENSORS:
+        raise ValueError(f"--grad_lowrank supports at most "
+                         f"{LOWRANK_MAX_TENSORS} compressed tensors, this "
+                         f"model has {len(plan)}")
+    return plan
+
+
+def lowrank_q_init(plan, R: int, seed: int):
+    """The start factors [Q of tensor 0 | Q of tensor 1 | ..], Q [cols][R]
+    standard normal keyed on (seed, tensor index): built on the host, so
+    every rank and every device holds the same bits."""
+    qs = []
+    for i, _, _, cols in plan:
+        gen = torch.Generator().manual_seed(int(seed) * 1000003 + 7919 * i + 1)
+        qs.append(torch.randn(cols, R, generator=gen).reshape(-1))
+    return torch.cat(qs)
+
+
+def lowrank_orth(P):
+    """Modified Gram-Schmidt of the columns of P, in column order, each column
+    divided by (its 2-norm + 1e-8) as in torch's PowerSGD hook, so a zero
+    column stays zero.  The divided column q is a little short of unit length,
+    so the projection of the later columns divides by q.q: rest -= (q.rest /
+    q.q) q.  (The hook leaves that division out; 2e-8 of every projection
+    then stays behind, and the same 1e-8 blows a dependent column, which is
+    nothing but that remainder, up to a norm of order one.)
+    Before a column is divided it is projected once more against all
+    finished columns: in fp32 a dependent column is rounding noise far above
+    1e-8, and without the second pass it would become a unit vector that is
+    not orthogonal to the others, so that P P^T were no projector."""
+    P = P.clone()
+    qqs = []
+    for i in range(P.shape[1]):
+        if i > 0:
+            done, qq = P[:, :i], torch.stack(qqs)
+            dots = (done * P[:, i:i + 1]).sum(0)
+            P[:, i] -= (done * torch.where(qq > 0, dots / qq,
+                                           torch.zeros_like(dots))).sum(1)
+        P[:, i] = P[:, i] / (torch.linalg.vector_norm(P[:, i]) + 1e-8)
+        q = P[:, i:i + 1]
+        qqs.append((q * q).sum())
+        if i + 1 < P.shape[1]:
+            dots = (q * P[:, i + 1:]).sum(0)
+            P[:, i + 1:] -= torch.where(qqs[i] > 0, dots / qqs[i],
+                                        torch.zeros_like(dots)) * q
+    return P
+
+
+def lowrank_step(G, E, Q, reduce=None):
+    """One PowerSGD step (Vogels et al. 2019) of one [rows][cols] tensor, the
+    contract of csrc/lowrank.hip, in the dtype of its inputs:
+      M = G + E;  P = M Q (summed over ranks);  P^ = lowrank_orth(P);
+      Q_r = M^T P^ (summed over ranks: Q_S);  bucket = P^ Q_S^T, the SUM of
+      the ranks' approximations;  E' = M - P^ Q_r^T, this rank's own share.
+    `reduce` sums a tensor over the ranks (None: one rank).  Returns (bucket,
+    E', Q_S, P^); Q_S is the next step's Q."""
+    M = G + E
+    P = M @ Q
+    if reduce is not None:
+        P = reduce(P)
+    Ph = lowrank_orth(P)
+    Qr = M.t() @ Ph
+    Qs = reduce(Qr) if reduce is not None else Qr
+    return Ph @ Qs.t(), M - Ph @ Qr.t(), Qs, Ph
+
+
 def lars_norm(master, flat, offsets, numels, adapt_mask: int,
               grad_scale: float, eta: float, wd: float, clip: float = 0.0):
     """LARS trust ratios (You, Gitman, Ginsburg 2017) of the flat fp32

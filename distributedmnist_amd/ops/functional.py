@@ -379,6 +379,109 @@ def topk_scatter(payloads: torch.Tensor, n: int, out=None):
     return out
 
 
+class LowrankState:
+    """--grad_lowrank R: the plan and the persistent buffers of PowerSGD
+    compression on one flat bucket of `n` values (ops/cpu_ref.py::lowrank_step
+    is the contract).  resid [n]: the error-feedback residual, zero over the
+    dense tensors; between lowrank_p and lowrank_expand it holds M = G + E.
+    q: the warm-start factors [Q_0 | Q_1 | ..], Q [cols][R].  wire: [P_0 |
+    P_1 | .. | dense tensors], P [rows][R]; the dense tail exists only with
+    `pack` (more than one rank), where wire and q are the two all-reduce
+    payloads.  qr: this rank's Q_r; without `pack` it IS q."""
+
+    def __init__(self, shapes, offsets, n: int, R: int, seed: int, device,
+                 pack: bool):
+        self.R, self.n, self.pack = int(R), int(n), bool(pack)
+        self.plan = cpu_ref.lowrank_plan(shapes, offsets, R)
+        if not self.plan:
+            raise ValueError("--grad_lowrank: no tensor of this model can be "
+                             "compressed")
+        self.offsets = [p[1] for p in self.plan]
+        self.rows = [p[2] for p in self.plan]
+        self.cols = [p[3] for p in self.plan]
+        # the dense gaps of the bucket, in order: (bucket offset, length)
+        self.gaps, at = [], 0
+        for o, r, c in zip(self.offsets, self.rows, self.cols):
+            if o > at:
+                self.gaps.append((at, o - at))
+            at = o + r * c
+        if n > at:
+            self.gaps.append((at, n - at))
+        self.p_floats = self.R * sum(self.rows)
+        self.q_floats = self.R * sum(self.cols)
+        self.dense_floats = sum(m for _, m in self.gaps)
+        self.resid = torch.zeros(n, dtype=torch.float32, device=device)
+        self.q = cpu_ref.lowrank_q_init(self.plan, R, seed).to(device)
+        self.qr = torch.zeros_like(self.q) if pack else self.q
+        self.wire = torch.zeros(
+            self.p_floats + (self.dense_floats if pack else 0),
+            dtype=torch.float32, device=device)
+
+    def views(self, flat, t, width=None):
+        """tensor t's matrix inside a bucket-shaped buffer (width None), or
+        its [.][R] factor inside wire (width = rows) / q (width = cols)"""
+        if width is None:
+            o, r, c = self.offsets[t], self.rows[t], self.cols[t]
+            return flat[o:o + r * c].view(r, c)
+        o = self.R * sum(width[:t])
+        return flat[o:o + width[t] * self.R].view(width[t], self.R)
+
+
+def lowrank_p(g: torch.Tensor, st: LowrankState):
+    """PowerSGD, first half: on every compressed tensor st.resid becomes M =
+    G + E and P = M Q goes into st.wire; with st.pack the dense tensors of
+    `g` are copied behind P, so that ONE all-reduce of st.wire sums both.  On
+    the GPU lowrank_p_kernel: one pass over G and E, fp32 MFMA."""
+    if g.is_cuda:
+        _C.ext().lowrank_p(g, st.resid, st.q, st.wire, st.offsets, st.rows,
+                           st.cols, st.R, pack=st.pack)
+        return
+    for t in range(len(st.plan)):
+        M = st.views(st.resid, t)
+        M += st.views(g, t)
+        st.views(st.wire, t, st.rows).copy_(M @ st.views(st.q, t, st.cols))
+    at = st.p_floats
+    for o, m in st.gaps if st.pack else ():
+        st.wire[at:at + m] = g[o:o + m]
+        at += m
+
+
+def lowrank_q(st: LowrankState):
+    """PowerSGD, between the two sums over ranks: P in st.wire is
+    orthonormalised in place (modified Gram-Schmidt), then st.qr = M^T P.  On
+    the GPU lowrank_orth_kernel + lowrank_q_kernel, fixed summation orders."""
+    if st.wire.is_cuda:
+        _C.ext().lowrank_q(st.resid, st.wire, st.qr, st.offsets, st.rows,
+                           st.cols, st.R)
+        return
+    for t in range(len(st.plan)):
+        P = st.views(st.wire, t, st.rows)
+        P.copy_(cpu_ref.lowrank_orth(P))
+        st.views(st.qr, t, st.cols).copy_(st.views(st.resid, t).t() @ P)
+
+
+def lowrank_expand(g: torch.Tensor, st: LowrankState):
+    """PowerSGD, last part: on every compressed tensor g = P Q_S^T (st.q, the
+    sum over ranks) and st.resid = M - P Q_r^T (st.qr); with one rank the
+    product is formed once and serves both.  With st.pack the summed dense
+    tensors return from st.wire into g.  On the GPU lowrank_expand_kernel."""
+    if g.is_cuda:
+        _C.ext().lowrank_expand(g, st.resid, st.wire, st.qr, st.q, st.offsets,
+                                st.rows, st.cols, st.R, pack=st.pack)
+        return
+    for t in range(len(st.plan)):
+        P = st.views(st.wire, t, st.rows)
+        M = st.views(st.resid, t)
+        own = P @ st.views(st.qr, t, st.cols).t()
+        st.views(g, t).copy_(
+            P @ st.views(st.q, t, st.cols).t() if st.pack else own)
+        M -= own
+    at = st.p_floats
+    for o, m in st.gaps if st.pack else ():
+        g[o:o + m] = st.wire[at:at + m]
+        at += m
+
+
 def lars_norm(master: torch.Tensor, flat: torch.Tensor, offsets, numels,
               adapt_mask: int, grad_scale: float, eta: float, wd: float,
               clip: float = 0.0, lars_tab=None, lars_stats=None,

@@ -48,7 +48,8 @@ class SyncEngine:
                  straggler_timeout_ms: float | None = None,
                  group=None, rank: int = 0, world_size: int = 1,
                  cdf_log_every: int = 50, cdf_start_tracking: int = 20,
-                 wire_dtype: torch.dtype | None = None, topk_pairs: int = 0):
+                 wire_dtype: torch.dtype | None = None, topk_pairs: int = 0,
+                 lowrank=None):
         if mode not in MODES:
             raise ValueError(f"mode {mode!r} not in {MODES}")
         # --grad_topk: the sparse exchange replaces the dense all-reduce.
@@ -68,6 +69,15 @@ class SyncEngine:
                 self.topk_gather = torch.zeros(
                     world_size, 2, topk_pairs, dtype=torch.int32,
                     device=flat_grad.device)
+        # --grad_lowrank: ops.functional.LowrankState; two small all-reduces
+        # of its wire and q buffers replace the dense one
+        self.lowrank = lowrank
+        if lowrank is not None and (
+                mode not in ("full_sync", "cdf") or wire_dtype is not None
+                or straggler_timeout_ms or topk_pairs > 0):
+            raise ValueError("the low-rank exchange serves full_sync / cdf "
+                             "with an fp32 wire, no straggler timeout and no "
+                             "top-k sparsification")
         self.mode = mode
         self.flat_grad = flat_grad
         self.group = group
@@ -155,6 +165,24 @@ class SyncEngine:
         Fx.topk_scatter(self.topk_gather, self.flat_grad.numel(),
                         out=self.flat_grad)
 
+    def lowrank_exchange(self):
+        """--grad_lowrank after ops.functional.lowrank_p: all-reduce of [P |
+        dense tensors], orthonormalisation and Q_r = M^T P, all-reduce of
+        Q_r, then bucket = P Q_S^T and the residual.  Two sums whatever the
+        world size; every rank holds the same P and Q_S, so all hold the same
+        bucket bits.  Also the eager half of the graphed split step.  With
+        one rank no collective: the two launches that remain."""
+        from ..ops import functional as Fx
+        st = self.lowrank
+        if self.distributed:
+            dist.all_reduce(st.wire, op=dist.ReduceOp.SUM, group=self.group)
+        Fx.lowrank_q(st)
+        if st.qr is not st.q:
+            st.q.copy_(st.qr)
+        if self.distributed:
+            dist.all_reduce(st.q, op=dist.ReduceOp.SUM, group=self.group)
+        Fx.lowrank_expand(self.flat_grad, st)
+
     # ------------------------------------------------------------------
     def step_begin(self, step: int):
         self._t_start = time.time()
@@ -205,6 +233,8 @@ class SyncEngine:
         if self.mode in ("full_sync", "cdf") and self.timeout_s is None:
             if self.topk_payload is not None:
                 self.sparse_exchange()
+            elif self.lowrank is not None:
+                self.lowrank_exchange()
             elif self.distributed:
                 if self.wire_dtype is None:
                     dist.all_reduce(self.flat_grad, op=dist.ReduceOp.SUM,

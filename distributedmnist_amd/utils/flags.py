@@ -62,6 +62,18 @@ def _grad_topk(text: str) -> float:
     return v
 
 
+def _grad_lowrank(text: str) -> int:
+    """--grad_lowrank: 0 (off) or a rank in 1..16."""
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not an integer: {text!r}")
+    if not 0 <= v <= 16:
+        raise argparse.ArgumentTypeError(
+            f"must be 0 (off) or lie in 1..16, got {text}")
+    return v
+
+
 def _adam_eps(text: str) -> float:
     """--adam_eps: finite and > 0."""
     try:
@@ -120,6 +132,20 @@ class _TrainParser(argparse.ArgumentParser):
                      "payload is index + fp32 value pairs)")):
                 if bad:
                     self.error(f"argument --grad_topk: not with {what}")
+        if ns.grad_lowrank > 0:
+            # as above: two small all-reduces replace the dense one
+            for bad, what in (
+                    (ns.grad_topk > 0, "--grad_topk (one compressor at a "
+                     "time)"),
+                    (ns.interval_method, "--interval_method (the interval "
+                     "accumulator is dense)"),
+                    ((ns.straggler_timeout_ms or 0) > 0,
+                     "--straggler_timeout_ms > 0 (a dropped factor would "
+                     "lose its residual)"),
+                    (ns.grad_dtype == "bf16", "--grad_dtype bf16 (the "
+                     "factors stay fp32)")):
+                if bad:
+                    self.error(f"argument --grad_lowrank: not with {what}")
         # the defaults, once the "was it given" check is done
         for name, default in (("adam_beta1", 0.9), ("adam_beta2", 0.999),
                               ("adam_eps", 1e-8)):
@@ -224,6 +250,20 @@ def build_train_parser() -> argparse.ArgumentParser:
                         "below the world size, --straggler_timeout_ms, "
                         "--grad_dtype bf16 or --hip_graph full at world > 1. "
                         "0 = off")
+    p.add_argument("--grad_lowrank", type=_grad_lowrank, default=0,
+                   metavar="R",
+                   help="R in 1..16: PowerSGD rank-R gradient compression "
+                        "with error feedback (Vogels, Karimireddy, Jaggi "
+                        "2019). Every weight matrix the kernels can tile "
+                        "(rows and cols multiples of 16, 64..4096 x 64..512) "
+                        "is sent as two thin fp32 factors in two small "
+                        "all-reduces, whatever the world size; what the "
+                        "factors miss stays in a local residual. All other "
+                        "tensors are sent exactly. fp32 MFMA kernels with "
+                        "fixed summation orders. Not with --grad_topk, "
+                        "--interval_method, --num_replicas_to_aggregate below "
+                        "the world size, --straggler_timeout_ms, --grad_dtype "
+                        "bf16 or --hip_graph full at world > 1. 0 = off")
     p.add_argument("--drop_connect_post", action="store_true",
                    help="legacy round-1 form: one shared mask on the "
                         "AGGREGATED gradient (default is the reference's "
