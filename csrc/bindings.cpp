@@ -1347,6 +1347,86 @@ void topk_scatter(torch::Tensor payload, torch::Tensor grad, bool assign) {
                       cur_stream());
 }
 
+// MXFP8 gradient wire (mxwire.hip).  Shared checks of the three ops: a uint8
+// buffer of `bytes` bytes on `like`'s device, 16-byte aligned.
+static uint8_t* mx_bytes(const char* who, const torch::Tensor& t,
+                         int64_t bytes, const torch::Tensor& like) {
+  CHECK_CUDA(t); CHECK_CONTIG(t);
+  TORCH_CHECK(t.scalar_type() == at::kByte && t.numel() == bytes, who,
+              ": expected ", bytes, " uint8 bytes, got ", t.numel());
+  TORCH_CHECK(t.get_device() == like.get_device(), who,
+              ": all tensors live on one device");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, who,
+              ": buffers must be 16-byte aligned");
+  return t.data_ptr<uint8_t>();
+}
+
+static const long* mx_step_dev(const c10::optional<torch::Tensor>& step_dev) {
+  if (!step_dev.has_value() || !step_dev->defined()) return nullptr;
+  TORCH_CHECK(step_dev->is_cuda() && step_dev->scalar_type() == at::kLong &&
+              step_dev->numel() >= 1, "mx: step_dev is a device int64 [1]");
+  return step_dev->data_ptr<long>();
+}
+
+static void mx_check_f32(const char* who, const torch::Tensor& x, int64_t world) {
+  CHECK_CUDA(x); CHECK_F32(x); CHECK_CONTIG(x);
+  TORCH_CHECK(x.numel() >= 1 && x.numel() < (int64_t(1) << 31), who,
+              ": 1 <= n < 2^31 elements");
+  TORCH_CHECK(world >= 1 && world <= 16, who, ": world must lie in 1..16");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0, who,
+              ": buffers must be 16-byte aligned");
+}
+
+void mx_encode(torch::Tensor x, torch::Tensor wire, int64_t world,
+               int64_t seed, int64_t step, int64_t stage, int64_t rank,
+               c10::optional<torch::Tensor> keep,
+               c10::optional<torch::Tensor> step_dev) {
+  mx_check_f32("mx_encode", x, world);
+  const int64_t n = x.numel();
+  const int64_t sb = mx_shard_blocks(n, (int)world);
+  uint8_t* w = mx_bytes("mx_encode", wire, world * 33 * sb, x);
+  TORCH_CHECK((stage == 0 || stage == 1) && rank >= 0 && rank < (1 << 20),
+              "mx_encode: stage is 0 or 1, rank in [0, 2^20)");
+  float* kp = nullptr;
+  if (keep.has_value() && keep->defined()) {
+    mx_check_f32("mx_encode", *keep, world);
+    TORCH_CHECK(keep->numel() == n && keep->get_device() == x.get_device(),
+                "mx_encode: keep holds n floats on x's device");
+    kp = keep->data_ptr<float>();
+  }
+  launch_mx_encode(x.data_ptr<float>(), n, (int)world, (uint64_t)seed,
+                   (uint64_t)step, mx_step_dev(step_dev), (int)stage,
+                   (int)rank, w, kp, cur_stream());
+}
+
+void mx_reduce(torch::Tensor rows, torch::Tensor shard, int64_t seed,
+               int64_t step, int64_t owner,
+               c10::optional<torch::Tensor> step_dev) {
+  CHECK_CUDA(shard);
+  const int64_t bytes = shard.numel();
+  TORCH_CHECK(bytes >= 33 * 16 && bytes % (33 * 16) == 0,
+              "mx_reduce: a shard is 33 * sb bytes, sb a multiple of 16");
+  TORCH_CHECK(bytes / 33 < (int64_t(1) << 26), "mx_reduce: shard too large");
+  const int64_t world = rows.numel() / bytes;
+  TORCH_CHECK(world >= 1 && world <= 16 && rows.numel() == world * bytes,
+              "mx_reduce: rows is uint8 [world][33 * sb], world in 1..16");
+  TORCH_CHECK(owner >= 0 && owner < (1 << 20),
+              "mx_reduce: owner in [0, 2^20)");
+  uint8_t* out = mx_bytes("mx_reduce", shard, bytes, shard);
+  const uint8_t* in = mx_bytes("mx_reduce", rows, world * bytes, shard);
+  launch_mx_reduce(in, (int)world, (int)(bytes / 33), (uint64_t)seed,
+                   (uint64_t)step, mx_step_dev(step_dev), (int)owner, out,
+                   cur_stream());
+}
+
+void mx_decode(torch::Tensor wire, int64_t world, torch::Tensor out) {
+  mx_check_f32("mx_decode", out, world);
+  const int64_t n = out.numel();
+  const int64_t sb = mx_shard_blocks(n, (int)world);
+  const uint8_t* w = mx_bytes("mx_decode", wire, world * 33 * sb, out);
+  launch_mx_decode(w, (int)world, n, out.data_ptr<float>(), cur_stream());
+}
+
 // PowerSGD rank-R compression (lowrank.hip).  The four ops share one
 // description of the bucket: the compressed matrices (offsets, rows, cols;
 // ascending, disjoint, each passing lowrank_fits), the rank, and `pack`: the
@@ -2295,6 +2375,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "grad[index] += value for the pairs of one payload [2][K]; assign: "
         "grad is zero, no load",
         py::arg("payload"), py::arg("grad"), py::arg("assign") = false);
+  m.def("mx_shard_blocks", [](int64_t n, int64_t world) {
+          TORCH_CHECK(n >= 1 && world >= 1 && world <= 16,
+                      "mx_shard_blocks: n >= 1, world in 1..16");
+          return mx_shard_blocks((long)n, (int)world);
+        }, "blocks per shard of the MXFP8 wire of n elements");
+  m.def("mx_encode", &mx_encode,
+        "MXFP8: x [n] -> wire uint8 [world][33 * sb] (32 e4m3 codes per E8M0 "
+        "scale byte, stochastic rounding keyed on seed, step, stage, rank, "
+        "index); keep: a copy of x; step_dev: the step, read on the device",
+        py::arg("x"), py::arg("wire"), py::arg("world"), py::arg("seed"),
+        py::arg("step"), py::arg("stage"), py::arg("rank"),
+        py::arg("keep") = c10::nullopt, py::arg("step_dev") = c10::nullopt);
+  m.def("mx_reduce", &mx_reduce,
+        "MXFP8: rows uint8 [world][33 * sb] of one shard decoded, added in "
+        "fp32 in row order and re-encoded (stage 1, rank owner) into shard",
+        py::arg("rows"), py::arg("shard"), py::arg("seed"), py::arg("step"),
+        py::arg("owner"), py::arg("step_dev") = c10::nullopt);
+  m.def("mx_decode", &mx_decode,
+        "MXFP8: wire uint8 [world][33 * sb] -> out fp32 [n], exactly",
+        py::arg("wire"), py::arg("world"), py::arg("out"));
   m.def("lowrank_p", &lowrank_p,
         "PowerSGD: resid = grad + resid (= M) on the compressed matrices, "
         "P = M q into wire; pack: the rest of grad is copied behind P",

@@ -28,7 +28,7 @@ def main():
              "data_gather.hip", "elastic_gather.hip", "conv2_dw_slab.hip", "conv2_resident.hip",
              "eval_ops.hip",
              "det_reduce.hip", "fc2_head.hip", "grad_norm.hip", "topk.hip", "lowrank.hip",
-             "lars.hip",
+             "lars.hip", "mxwire.hip",
              "adam.hip", "muon.hip", "bindings.cpp")]
     out = os.path.join(ROOT, "_dmnist_hip.so")
 

@@ -296,6 +296,27 @@ void launch_topk_compress(float* grad, float* resid, long n, GradNormSegs segs,
 // assign: grad is known to be zero, grad[index] = 0 + value without the load
 void launch_topk_scatter(const int* payload, int K, float* grad, long n,
                          int assign, hipStream_t);
+// mxwire.hip — MXFP8 gradient wire (--grad_dtype mxfp8): blocks of 32 e4m3
+// codes with one E8M0 scale byte, stochastic rounding keyed on (seed, step,
+// stage, rank, element index); bit-exact with ops/cpu_ref.py::mx_*.  wire:
+// uint8 [world][33 * sb], sb = mx_shard_blocks(n, world) (a multiple of 16),
+// shard w = 32 * sb code bytes of blocks [w * sb, (w + 1) * sb), then their
+// sb scale bytes.  All pointers 16 B aligned, n < 2^31, world <= 16; step_dev
+// (optional) replaces step, read on the device.
+//   mx_encode: x [n] -> wire (padding blocks written as zeros); keep
+//              (optional, [n]) receives a copy of x
+//   mx_reduce: rows [world][33 * sb] of ONE shard -> shard [33 * sb]: decoded,
+//              added in fp32 in row order, re-encoded with stage 1, rank owner
+//   mx_decode: wire -> out [n], nothing written past n
+int mx_shard_blocks(long n, int world);
+void launch_mx_encode(const float* x, long n, int world, uint64_t seed,
+                      uint64_t step, const long* step_dev, int stage, int rank,
+                      uint8_t* wire, float* keep, hipStream_t);
+void launch_mx_reduce(const uint8_t* rows, int world, int sb, uint64_t seed,
+                      uint64_t step, const long* step_dev, int owner,
+                      uint8_t* shard, hipStream_t);
+void launch_mx_decode(const uint8_t* wire, int world, long n, float* out,
+                      hipStream_t);
 // lowrank.hip — PowerSGD rank-R compression of the flat fp32 gradient with
 // error feedback (--grad_lowrank).  Up to LOWRANK_MAX_TENSORS row-major
 // [rows][cols] matrices of the bucket that pass lowrank_fits, ascending and

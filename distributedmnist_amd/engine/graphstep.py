@@ -131,6 +131,13 @@ class GraphedStep:
                                                t.flat_lowrank_q)]
             assert split or not t.engine.distributed, \
                 "--grad_lowrank at world > 1 needs the split capture scope"
+        # --grad_dtype mxfp8: no state to roll back.  With one rank encode and
+        # decode sit in the captured body; with more the exchange runs
+        # eagerly between the captured encode and the tail
+        self._mx = bool(getattr(t, "mx", False))
+        if self._mx:
+            assert split or not t.engine.distributed, \
+                "--grad_dtype mxfp8 at world > 1 needs the split capture scope"
         t.model.set_step_dev(self.step_dev)
 
         if self.split and self._fused is not None:
@@ -143,7 +150,8 @@ class GraphedStep:
             # fall back to the post-body whole-bucket reduce in _body
             # (only reachable via --hip_graph full at world > 1)
             self._fused.overlap_allreduce = False
-        if (self._topk or self._lowrank) and self._fused is not None:
+        if ((self._topk or self._lowrank or self._mx)
+                and self._fused is not None):
             # as in eager mode: the sparse exchange replaces the all-reduce
             self._fused.overlap_allreduce = False
 
@@ -181,6 +189,7 @@ class GraphedStep:
         self.two_graph = (self.split and self._fused is not None
                           and not self._topk  # whole-bucket selection
                           and not self._lowrank
+                          and not self._mx
                           and _os.environ.get("DMNIST_SPLIT2", "1") != "0")
         fp = t.fp
         fc0 = fp.offsets[fp.names.index("fc1_w")]
@@ -342,6 +351,15 @@ class GraphedStep:
             Fx.lowrank_p(fp.flat_grad, t.lowrank)
             if not self.split:
                 t.engine.lowrank_exchange()
+        if self._mx:
+            # the key's step is read from step_dev; every other argument is
+            # a capture constant
+            from ..ops import functional as Fx
+            Fx.mx_encode(fp.flat_grad, t.flags.seed, 0, 0, t.rank, t.world,
+                         out=t.engine.mx_send, keep=t.engine.mx_keep,
+                         step_dev=self.step_dev)
+            if not self.split:
+                t.engine.mx_exchange(0, step_dev=self.step_dev)
         self.static_loss = loss.detach()
         self.static_acc = acc.detach()
         return fused_reduced
@@ -471,6 +489,8 @@ class GraphedStep:
                 t.engine.sparse_exchange()
             elif self._lowrank:
                 t.engine.lowrank_exchange()
+            elif self._mx:
+                t.engine.mx_exchange(0, step_dev=self.step_dev)
             elif t.world > 1 and dist.is_initialized():
                 t.engine.wire_allreduce(t.fp.flat_grad)
             self._tail()

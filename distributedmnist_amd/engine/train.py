@@ -188,8 +188,8 @@ class Trainer:
             if (flags.straggler_timeout_ms or 0) > 0:
                 conflict("--straggler_timeout_ms > 0",
                          "a dropped payload would lose its residual")
-            if getattr(flags, "grad_dtype", "fp32") == "bf16":
-                conflict("--grad_dtype bf16",
+            if getattr(flags, "grad_dtype", "fp32") != "fp32":
+                conflict(f"--grad_dtype {flags.grad_dtype}",
                          "the payload is index + fp32 value pairs")
             if world > 1 and getattr(flags, "hip_graph", "auto") == "full":
                 conflict("--hip_graph full at world > 1",
@@ -227,8 +227,9 @@ class Trainer:
             if (flags.straggler_timeout_ms or 0) > 0:
                 conflict("--straggler_timeout_ms > 0",
                          "a dropped factor would lose its residual")
-            if getattr(flags, "grad_dtype", "fp32") == "bf16":
-                conflict("--grad_dtype bf16", "the factors stay fp32")
+            if getattr(flags, "grad_dtype", "fp32") != "fp32":
+                conflict(f"--grad_dtype {flags.grad_dtype}",
+                         "the factors stay fp32")
             if world > 1 and getattr(flags, "hip_graph", "auto") == "full":
                 conflict("--hip_graph full at world > 1",
                          "the exchange runs between the captured gradients "
@@ -238,10 +239,39 @@ class Trainer:
                 self.lowrank_rank, flags.seed, self.device, pack=world > 1)
             self.flat_lowrank_residual = self.lowrank.resid
             self.flat_lowrank_q = self.lowrank.q
+        # --grad_dtype mxfp8: the bucket travels as OCP MXFP8 (ops.functional.
+        # mx_encode).  At the same place as top-k: encoded with unbiased
+        # stochastic rounding keyed on (seed, step, rank), exchanged by the
+        # engine as a quantised reduce-scatter and all-gather, and decoded
+        # from the same bytes on every rank; no residual, no new state.
+        self.mx = getattr(flags, "grad_dtype", "fp32") == "mxfp8"
+        if self.mx:
+            def conflict(what, why):
+                raise ValueError(f"--grad_dtype mxfp8 cannot be combined "
+                                 f"with {what}: {why}")
+            if mode == "interval":
+                conflict("--interval_method",
+                         "the interval accumulator is dense")
+            if mode == "k_of_n":
+                conflict("--num_replicas_to_aggregate below the world size",
+                         "the contributor flag cannot ride in a quantised "
+                         "buffer")
+            if (flags.straggler_timeout_ms or 0) > 0:
+                conflict("--straggler_timeout_ms > 0",
+                         "the contributor flag cannot ride in a quantised "
+                         "buffer")
+            if world > 1 and getattr(flags, "hip_graph", "auto") == "full":
+                conflict("--hip_graph full at world > 1",
+                         "the exchange runs between the captured gradients "
+                         "and the update")
+            if world > 16:
+                raise ValueError("--grad_dtype mxfp8 supports at most 16 "
+                                 "ranks")
         self.engine = SyncEngine(
             self.fp.flat_grad, mode=mode,
             topk_pairs=sum(self.topk_ks) if self.topk_ks else 0,
             lowrank=self.lowrank,
+            mx_seed=flags.seed if self.mx else None,
             replicas_to_aggregate=flags.num_replicas_to_aggregate,
             interval_ms=flags.interval_ms,
             straggler_timeout_ms=(flags.straggler_timeout_ms or None),
@@ -503,7 +533,7 @@ class Trainer:
             # runs between the captured gradients and the tail
             split = (self.world > 1 and dist.is_initialized()
                      and (not force_full or self.topk_ks is not None
-                          or self.lowrank is not None))
+                          or self.lowrank is not None or self.mx))
             self._graph = try_graph(self, batch_shape, split=split,
                                     dataset=self._resident_ds)
         if self.world > 1 and dist.is_initialized():
@@ -648,6 +678,11 @@ class Trainer:
         if self.lowrank is not None:
             # M = G + E and P = M Q; the engine's reduce does the rest
             Fx.lowrank_p(self.fp.flat_grad, self.lowrank)
+        if self.mx:
+            # this rank's wire; the engine's reduce exchanges and decodes it
+            Fx.mx_encode(self.fp.flat_grad, flags.seed, self.step, 0,
+                         self.rank, self.world, out=self.engine.mx_send,
+                         keep=self.engine.mx_keep)
         compute_time = self.timer.stop() if timed else 0.0
         applied, grad, contributors = self.engine.reduce(self.step, compute_time)
         if applied:
@@ -776,6 +811,22 @@ class Trainer:
         return {name: (k, thr, kept / total if total > 0 else 1.0)
                 for name, k, (thr, kept, total)
                 in zip(self.fp.names, self.topk_ks, s)}
+
+    def mx_stats(self):
+        """{tensor name: |decode(encode(g)) - g| / |g|} of the most recent
+        step under --grad_dtype mxfp8: the relative L2 error of this rank's
+        own encode of its gradient g (0 for an all-zero tensor).  Decoded from
+        the send buffer and reduced on the device, then one read: for tools
+        and tests, not for the step loop."""
+        if not self.mx:
+            raise RuntimeError("mx_stats() needs --grad_dtype mxfp8")
+        g = self.engine.mx_keep.double()
+        d = Fx.mx_decode(self.engine.mx_send, g.numel()).double() - g
+        s = torch.stack([
+            torch.stack([d[o:o + m].square().sum(), g[o:o + m].square().sum()])
+            for o, m in zip(self.fp.offsets, self.fp.numels)]).cpu().tolist()
+        return {name: (err / ref) ** 0.5 if ref > 0 else 0.0
+                for name, (err, ref) in zip(self.fp.names, s)}
 
     def lowrank_stats(self):
         """{tensor name: (rank, |E| / |M|)} of the compressed tensors after

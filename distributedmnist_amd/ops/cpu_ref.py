@@ -1209,3 +1209,153 @@ def plane_reduce(planes, out):
         s = s + p[i]
     out += s.to(out.device).view_as(out)
     return out
+
+
+# ---------------------------------------------------------------------------
+# MXFP8 gradient wire (--grad_dtype mxfp8): the bit-exact contract of
+# csrc/mxwire.hip (docs/KERNELS.md "MXFP8 gradient wire").  OCP MX: blocks of
+# 32 e4m3 codes, one E8M0 scale byte per block; stochastic rounding in integer
+# arithmetic on the fp32 bits, nothing ever clipped.
+# ---------------------------------------------------------------------------
+
+MX_BLOCK = 32
+MX_KEY_ADD = 0x4D58F8E4
+MX_NAN_BITS = 0x7FC00000
+
+
+def mx_shard_blocks(n: int, world: int) -> int:
+    """Blocks per shard: ceil(ceil(n / 32) / world) rounded up to a multiple
+    of 16, so a shard (32 * sb code bytes, then sb scale bytes) is a multiple
+    of 16 B."""
+    if n < 1 or not 1 <= world <= 16:
+        raise ValueError(f"mx_shard_blocks: n = {n} >= 1, world = {world} in "
+                         "1..16")
+    nb = -(-n // MX_BLOCK)
+    return (-(-nb // world) + 15) // 16 * 16
+
+
+def mx_key(seed: int, step: int, stage: int, rank: int) -> int:
+    """The 32-bit rounding key of one encode: the seed fold and the 64-bit
+    step fold of the batch gathers' position keys (MX_KEY_ADD separates the
+    users), then the (rank, stage) pair.  Element i draws
+    _mix32(key + i * 0x85EBCA6B)."""
+    seed &= 0xFFFFFFFFFFFFFFFF
+    step &= 0xFFFFFFFFFFFFFFFF
+    base = _mix32((seed & _M32) ^ _mix32(((seed >> 32) + 0x9E3779B9) & _M32))
+    k = _mix32((base + MX_KEY_ADD + (step & _M32) * 0x9E3779B1) & _M32)
+    k = _mix32(k ^ _mix32(((step >> 32) + 0x7F4A7C15) & _M32))
+    return _mix32((k + (2 * rank + stage + 1) * 0xC2B2AE35) & _M32)
+
+
+def mx_encode(x, seed: int, step: int, stage: int, rank: int):
+    """Flat fp32 [n] -> (codes uint8 [32 * nb], scales uint8 [nb]), nb =
+    ceil(n / 32); elements past n count as zero.
+
+    Scale byte of a block from A = max(bits & 0x7fffffff): 0xFF when A >=
+    0x7f800000 (a non-finite element; all codes 0), otherwise
+    max(0, (A >> 23) - 8 + ((A & 0x7fffff) > 0x600000)): e = byte - 127 is the
+    smallest integer in [-127, 127] with amax * 2^-e <= 448 = 1.75 * 2^8.
+
+    Element: sign, exponent field ef and significand M (24 bits, bit 23 set;
+    a subnormal is normalised: M = mant << lz, ef = 1 - lz; zero has M = 0) of
+    its fp32 bits.  k = ef - 127 - e is the binade of y = x * 2^-e, sh = 20 +
+    max(0, -6 - k) the significand bits below the e4m3 grid (capped at 63),
+    T = (M << 32) >> sh in 64 bits: q = T >> 32 grid steps toward zero, and
+    one more when the element's random word is below the low 32 bits of T
+    (probability remainder / step; exact for sh <= 32, truncated below
+    2^-32 of a step beyond, never for sh >= 56).  The magnitude is q * 2^
+    (max(k, -6) - 3): code (k + 7) << 3 plus q - 8 for k >= -6 (q = 16 carries
+    into the next binade), q itself in the subnormal range; a zero magnitude
+    drops the sign."""
+    import numpy as np
+    if x.dtype != torch.float32 or x.dim() != 1 or x.numel() < 1:
+        raise ValueError("mx_encode: x is a non-empty 1-D fp32 tensor")
+    n = x.numel()
+    nb = -(-n // MX_BLOCK)
+    bits = np.zeros(nb * MX_BLOCK, dtype=np.uint32)
+    bits[:n] = x.detach().cpu().contiguous().numpy().view(np.uint32)
+    mag = (bits & np.uint32(0x7FFFFFFF)).astype(np.int64)
+    A = mag.reshape(nb, MX_BLOCK).max(axis=1)
+    nonfinite = A >= 0x7F800000
+    byte = np.maximum(0, (A >> 23) - 8 + ((A & 0x7FFFFF) > 0x600000))
+    e = np.repeat(byte - 127, MX_BLOCK)
+    ef = mag >> 23
+    mant = mag & 0x7FFFFF
+    sub = ef == 0
+    lz = 24 - np.frexp(mant.astype(np.float64))[1].astype(np.int64)
+    M = np.where(sub, mant << np.where(sub, lz, 0), mant | 0x800000)
+    ef = np.where(sub, 1 - lz, ef)
+    k = ef - 127 - e
+    sh = np.minimum(63, 20 + np.maximum(0, -6 - k))
+    T = (M.astype(np.uint64) << np.uint64(32)) >> sh.astype(np.uint64)
+    key = mx_key(seed, step, stage, rank)
+    i = np.arange(nb * MX_BLOCK, dtype=np.uint64)
+    rnd = _mix32((np.uint64(key) + i * np.uint64(0x85EBCA6B))
+                 & np.uint64(_M32))
+    q = (T >> np.uint64(32)).astype(np.int64) + (
+        rnd < (T & np.uint64(_M32))).astype(np.int64)
+    code = np.where(k >= -6, ((k + 7) << 3) + q - 8, q)
+    code = np.where(q == 0, 0, code | ((bits >> 24) & 0x80))
+    code = np.where(np.repeat(nonfinite, MX_BLOCK), 0, code)
+    scales = np.where(nonfinite, 0xFF, byte)
+    return (torch.from_numpy(code.astype(np.uint8)),
+            torch.from_numpy(scales.astype(np.uint8)))
+
+
+def mx_decode(codes, scales):
+    """(codes uint8 [32 * nb], scales uint8 [nb]) -> fp32 [32 * nb], exactly:
+    e4m3 value * 2^(byte - 127), computed in float64 (every result is an fp32
+    number, subnormal ones included; only a code above 1.875 * 2^7 under byte
+    247 leaves the range and gives inf).  Scale byte 0xFF and the e4m3 NaN
+    codes (0x7F, 0xFF) give the NaN 0x7fc00000."""
+    import numpy as np
+    c = codes.detach().cpu().numpy().astype(np.int64)
+    s = scales.detach().cpu().numpy().astype(np.int64)
+    if c.size != s.size * MX_BLOCK:
+        raise ValueError("mx_decode: 32 codes per scale byte")
+    E, m = (c >> 3) & 15, c & 7
+    v = np.where(E == 0, np.ldexp(m.astype(np.float64), -9),
+                 np.ldexp((8 + m).astype(np.float64), E - 10))
+    v = np.where(c & 0x80, -v, v)
+    sb = np.repeat(s, MX_BLOCK)
+    with np.errstate(over="ignore"):
+        out = np.ldexp(v, sb - 127).astype(np.float32)
+    nan = np.uint32(MX_NAN_BITS).view(np.float32)
+    out = np.where((sb == 0xFF) | ((c & 0x7F) == 0x7F), nan, out)
+    return torch.from_numpy(out.astype(np.float32))
+
+
+def mx_to_wire(codes, scales, world: int):
+    """The shard layout of one encoded vector: uint8 [world][33 * sb], row w
+    = the 32 * sb code bytes of blocks [w * sb, (w + 1) * sb), then their sb
+    scale bytes; blocks past nb are zero (codes and scale)."""
+    nb = scales.numel()
+    sb = (-(-nb // world) + 15) // 16 * 16
+    c = torch.zeros(world * sb, MX_BLOCK, dtype=torch.uint8)
+    s = torch.zeros(world * sb, dtype=torch.uint8)
+    c[:nb] = codes.view(nb, MX_BLOCK)
+    s[:nb] = scales
+    return torch.cat([c.view(world, sb * MX_BLOCK), s.view(world, sb)], dim=1)
+
+
+def mx_from_wire(wire):
+    """uint8 [W][33 * sb] (or one row [33 * sb]) -> (codes [32 * W * sb],
+    scales [W * sb]), the blocks in bucket order."""
+    wire = wire.reshape(-1, wire.shape[-1])
+    sb = wire.shape[1] // (MX_BLOCK + 1)
+    return (wire[:, :sb * MX_BLOCK].reshape(-1).contiguous(),
+            wire[:, sb * MX_BLOCK:].reshape(-1).contiguous())
+
+
+def mx_reduce(payloads, seed: int, step: int, owner: int):
+    """The owner's half of the exchange: payloads uint8 [W][33 * sb], row r =
+    rank r's encoding of the owner's shard.  Decodes every row, adds in fp32
+    in rank order (row 0, then + row 1, ...), and re-encodes the sum with
+    stage 1 and rank = owner (element indices local to the shard) -> uint8
+    [33 * sb]."""
+    payloads = payloads.reshape(-1, payloads.shape[-1])
+    acc = None
+    for row in payloads:
+        v = mx_decode(*mx_from_wire(row))
+        acc = v if acc is None else acc + v
+    return mx_to_wire(*mx_encode(acc, seed, step, 1, owner), 1)[0]

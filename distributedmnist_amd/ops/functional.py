@@ -379,6 +379,71 @@ def topk_scatter(payloads: torch.Tensor, n: int, out=None):
     return out
 
 
+def mx_encode(x: torch.Tensor, seed: int, step: int, stage: int, rank: int,
+              world: int = 1, out=None, keep=None, step_dev=None):
+    """MXFP8 wire of the flat fp32 vector `x` (ops/cpu_ref.py::mx_encode is
+    the contract): uint8 [world][33 * sb] in the shard layout of
+    cpu_ref.mx_to_wire, 32 e4m3 codes per E8M0 scale byte, rounded
+    stochastically under the key (seed, step, stage, rank, element index).
+    `out` is written in place when given; `keep` (fp32 [n], optional) receives
+    a copy of x.  On the GPU one mx_encode_kernel launch, hipGraph-capturable;
+    `step_dev` (int64 [1]) then replaces `step`, read on the device."""
+    n = x.numel()
+    sb = cpu_ref.mx_shard_blocks(n, world)
+    if out is None:
+        out = torch.empty(world, 33 * sb, dtype=torch.uint8, device=x.device)
+    if x.is_cuda:
+        _C.ext().mx_encode(x, out, int(world), int(seed), int(step),
+                           int(stage), int(rank), keep=keep,
+                           step_dev=step_dev)
+    else:
+        if step_dev is not None:
+            step = int(step_dev.item())
+        out.copy_(cpu_ref.mx_to_wire(
+            *cpu_ref.mx_encode(x, seed, step, stage, rank), world))
+        if keep is not None:
+            keep.copy_(x)
+    return out
+
+
+def mx_reduce(rows: torch.Tensor, seed: int, step: int, owner: int, out=None,
+              step_dev=None):
+    """One shard of the MXFP8 exchange: `rows` uint8 [W][33 * sb] (row r =
+    rank r's encoding of this shard) decoded, added in fp32 in rank order and
+    re-encoded with stage 1 and rank = owner -> uint8 [33 * sb]
+    (ops/cpu_ref.py::mx_reduce).  On the GPU one mx_reduce_kernel launch; the
+    fp32 sum stays in registers."""
+    rows = rows.reshape(-1, rows.shape[-1])
+    if out is None:
+        out = torch.empty(rows.shape[1], dtype=torch.uint8, device=rows.device)
+    if rows.is_cuda:
+        _C.ext().mx_reduce(rows, out, int(seed), int(step), int(owner),
+                           step_dev=step_dev)
+    else:
+        if step_dev is not None:
+            step = int(step_dev.item())
+        out.copy_(cpu_ref.mx_reduce(rows, seed, step, owner))
+    return out
+
+
+def mx_decode(wire: torch.Tensor, n: int, out=None):
+    """fp32 [n] of an MXFP8 wire uint8 [W][33 * sb], exactly
+    (ops/cpu_ref.py::mx_decode); `out` is written in place when given and
+    nothing is written past n.  On the GPU one mx_decode_kernel launch."""
+    wire = wire.reshape(-1, wire.shape[-1])
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=wire.device)
+    if out.numel() != n or wire.shape[1] != 33 * cpu_ref.mx_shard_blocks(
+            n, wire.shape[0]):
+        raise ValueError(f"mx_decode: wire {tuple(wire.shape)} / out "
+                         f"{out.numel()} do not hold {n} values")
+    if wire.is_cuda:
+        _C.ext().mx_decode(wire, wire.shape[0], out)
+    else:
+        out.copy_(cpu_ref.mx_decode(*cpu_ref.mx_from_wire(wire))[:n])
+    return out
+
+
 class LowrankState:
     """--grad_lowrank R: the plan and the persistent buffers of PowerSGD
     compression on one flat bucket of `n` values (ops/cpu_ref.py::lowrank_step

@@ -49,7 +49,7 @@ class SyncEngine:
                  group=None, rank: int = 0, world_size: int = 1,
                  cdf_log_every: int = 50, cdf_start_tracking: int = 20,
                  wire_dtype: torch.dtype | None = None, topk_pairs: int = 0,
-                 lowrank=None):
+                 lowrank=None, mx_seed: int | None = None):
         if mode not in MODES:
             raise ValueError(f"mode {mode!r} not in {MODES}")
         # --grad_topk: the sparse exchange replaces the dense all-reduce.
@@ -78,6 +78,32 @@ class SyncEngine:
             raise ValueError("the low-rank exchange serves full_sync / cdf "
                              "with an fp32 wire, no straggler timeout and no "
                              "top-k sparsification")
+        # --grad_dtype mxfp8 (mx_seed given): the quantised exchange replaces
+        # the dense all-reduce.  mx_send is this rank's encoding of the
+        # bucket, uint8 [W][33 * sb], written by ops.functional.mx_encode;
+        # mx_keep the fp32 gradient it encoded (Trainer.mx_stats).  With more
+        # than one rank: mx_recv the W encodings of this rank's shard, mx_shard
+        # their requantised sum, mx_gather every rank's shard.
+        self.mx_seed = mx_seed
+        self.mx_send = self.mx_keep = None
+        self.mx_recv = self.mx_shard = self.mx_gather = None
+        if mx_seed is not None:
+            if (mode not in ("full_sync", "cdf") or wire_dtype is not None
+                    or straggler_timeout_ms or topk_pairs > 0
+                    or lowrank is not None):
+                raise ValueError("the MXFP8 exchange serves full_sync / cdf "
+                                 "with no straggler timeout and no other "
+                                 "compressor")
+            from ..ops import cpu_ref
+            n = flat_grad.numel()
+            sb = cpu_ref.mx_shard_blocks(n, world_size)
+            u8 = dict(dtype=torch.uint8, device=flat_grad.device)
+            self.mx_send = torch.zeros(world_size, 33 * sb, **u8)
+            self.mx_keep = torch.zeros_like(flat_grad)
+            if world_size > 1:
+                self.mx_recv = torch.zeros(world_size, 33 * sb, **u8)
+                self.mx_shard = torch.zeros(33 * sb, **u8)
+                self.mx_gather = torch.zeros(world_size, 33 * sb, **u8)
         self.mode = mode
         self.flat_grad = flat_grad
         self.group = group
@@ -183,6 +209,27 @@ class SyncEngine:
             dist.all_reduce(st.q, op=dist.ReduceOp.SUM, group=self.group)
         Fx.lowrank_expand(self.flat_grad, st)
 
+    def mx_exchange(self, step: int, step_dev=None):
+        """--grad_dtype mxfp8 after ops.functional.mx_encode wrote mx_send:
+        all-to-all of the shards, the W encodings of this rank's shard summed
+        in fp32 in rank order and requantised (stage 1, keyed on the owner),
+        all-gather of the shards, decode into the bucket.  Every rank, the
+        owner included, decodes the same bytes, so all hold the same bits.
+        Also the eager half of the graphed split step (step_dev: the device
+        step counter).  With one rank no collective: the bucket becomes the
+        decode of its own encoding."""
+        from ..ops import functional as Fx
+        n = self.flat_grad.numel()
+        if not self.distributed:
+            Fx.mx_decode(self.mx_send, n, out=self.flat_grad)
+            return
+        dist.all_to_all_single(self.mx_recv, self.mx_send, group=self.group)
+        Fx.mx_reduce(self.mx_recv, self.mx_seed, step, self.rank,
+                     out=self.mx_shard, step_dev=step_dev)
+        dist.all_gather_into_tensor(self.mx_gather.view(-1), self.mx_shard,
+                                    group=self.group)
+        Fx.mx_decode(self.mx_gather, n, out=self.flat_grad)
+
     # ------------------------------------------------------------------
     def step_begin(self, step: int):
         self._t_start = time.time()
@@ -235,6 +282,8 @@ class SyncEngine:
                 self.sparse_exchange()
             elif self.lowrank is not None:
                 self.lowrank_exchange()
+            elif self.mx_send is not None:
+                self.mx_exchange(step)
             elif self.distributed:
                 if self.wire_dtype is None:
                     dist.all_reduce(self.flat_grad, op=dist.ReduceOp.SUM,

@@ -128,8 +128,8 @@ class _TrainParser(argparse.ArgumentParser):
                     ((ns.straggler_timeout_ms or 0) > 0,
                      "--straggler_timeout_ms > 0 (a dropped payload would "
                      "lose its residual)"),
-                    (ns.grad_dtype == "bf16", "--grad_dtype bf16 (the "
-                     "payload is index + fp32 value pairs)")):
+                    (ns.grad_dtype != "fp32", f"--grad_dtype {ns.grad_dtype} "
+                     "(the payload is index + fp32 value pairs)")):
                 if bad:
                     self.error(f"argument --grad_topk: not with {what}")
         if ns.grad_lowrank > 0:
@@ -142,10 +142,22 @@ class _TrainParser(argparse.ArgumentParser):
                     ((ns.straggler_timeout_ms or 0) > 0,
                      "--straggler_timeout_ms > 0 (a dropped factor would "
                      "lose its residual)"),
-                    (ns.grad_dtype == "bf16", "--grad_dtype bf16 (the "
-                     "factors stay fp32)")):
+                    (ns.grad_dtype != "fp32", f"--grad_dtype {ns.grad_dtype} "
+                     "(the factors stay fp32)")):
                 if bad:
                     self.error(f"argument --grad_lowrank: not with {what}")
+        if ns.grad_dtype == "mxfp8":
+            # the quantised reduce-scatter / all-gather replaces the dense
+            # synchronous all-reduce only (the checks that need the world
+            # size: Trainer)
+            for bad, what in (
+                    (ns.interval_method, "--interval_method (the interval "
+                     "accumulator is dense)"),
+                    ((ns.straggler_timeout_ms or 0) > 0,
+                     "--straggler_timeout_ms > 0 (the contributor flag "
+                     "cannot ride in a quantised buffer)")):
+                if bad:
+                    self.error(f"argument --grad_dtype mxfp8: not with {what}")
         # the defaults, once the "was it given" check is done
         for name, default in (("adam_beta1", 0.9), ("adam_beta2", 0.999),
                               ("adam_eps", 1e-8)):
@@ -232,9 +244,20 @@ def build_train_parser() -> argparse.ArgumentParser:
     p.add_argument("--fused_step", default="auto", choices=["auto", "off"],
                    help="hand-scheduled two-stream LeNet step inside the graph")
     p.add_argument("--backend", default="auto", help="auto|nccl|gloo")
-    p.add_argument("--grad_dtype", default="fp32", choices=["fp32", "bf16"],
+    p.add_argument("--grad_dtype", default="fp32",
+                   choices=["fp32", "bf16", "mxfp8"],
                    help="all-reduce wire dtype: bf16 halves the xGMI payload "
-                        "(6.65->3.33 MB); the fp32 master update is unchanged")
+                        "(6.65->3.33 MB); the fp32 master update is "
+                        "unchanged. mxfp8: OCP MXFP8 (e4m3 codes, one E8M0 "
+                        "scale per 32 elements) with unbiased stochastic "
+                        "rounding; a quantised reduce-scatter (all-to-all, "
+                        "sum in fp32, requantise) and all-gather replace the "
+                        "all-reduce and every rank decodes the same bytes. "
+                        "With one rank the bucket is encoded and decoded in "
+                        "place. Not with --grad_topk, --grad_lowrank, "
+                        "--interval_method, --num_replicas_to_aggregate "
+                        "below the world size, --straggler_timeout_ms or "
+                        "--hip_graph full at world > 1")
     p.add_argument("--grad_topk", type=_grad_topk, default=0.0,
                    metavar="RATIO",
                    help="RATIO in (0, 1]: top-k gradient sparsification with "
